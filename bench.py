@@ -19,7 +19,17 @@ Contract: W untimed warm-up passes, then exactly K timed passes bracketed by bar
 torch.cuda.synchronize() on both sides; MAX over ranks; rank 0 prints ONE JSON line.
 Inputs (population, theta) are resident in HBM before the timed region starts.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up (including the choice of the prediction buffer), warm-up, the K
+timed passes, `--dump-outputs` if given, and the line.  `--full` adds everything else the line can carry: the parity
+sample against the CPU oracle (exit code 3 when it fails), `cpu_baseline`, the device's measured write ceiling and the
+`roofline` object; without it those fields are null.
+
+--dump-outputs DIR: after the timed passes, what the last one computed (the arrays a caller of the timed path receives:
+predictions or log-likelihoods, and the status bytes) is written as DIR/<name>.npy, predictions in float64, status in
+float32.  Where the whole would pass 64 MB, every array keeps the same fixed, seeded sample of its rows and
+DIR/<name>_rows.npy lists them.  The inputs are seeded, so two builds can be compared output for output.
+
+Extra objects on the line (--full):
   roofline      dominant kernel vs the roofline that bounds it.  "hbm" (C3, C2): achieved = algorithmic bytes
                 per launch (8*S*O*P + 8*P*k + 26*S*E) / mean launch duration measured with HIP events
                 on the launch stream inside the timed region; peak = 8 TB/s.  "fp64_valu" (C5, C4, --ragged:
@@ -44,9 +54,36 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-# FP64 vector issue: one wave64 instruction per 4 cycles per SIMD; 256 CUs x 4 SIMDs; 2.4 GHz max clock (same guide)
+HBM_PEAK_GBS = 8000.0  # MI355X datasheet: HBM3E 8.0 TB/s
+# FP64 vector issue: one wave64 instruction per 4 cycles per SIMD; 256 CUs x 4 SIMDs; 2.4 GHz max clock (same datasheet)
 FP64_VALU_PEAK_GINST = 1024 * 2.4 / 4.0
+DUMP_BYTES = 60_000_000  # --dump-outputs: all arrays of one run together, so that the files stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: every CUDA tensor of `arrays` -> out_dir/<name>.npy (float64 stays float64, anything else becomes
+    float32).  When the whole set would pass DUMP_BYTES, every array keeps the same fraction of its rows, drawn with a
+    fixed seed, and out_dir/<name>_rows.npy holds their indices.  Ranks of an N > 1 run write <name>_rank<r>.npy, each
+    within its share of the budget."""
+    import numpy as np
+    import torch
+
+    from pharmsol_amd import synth
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // world
+    sfx = "" if world == 1 else f"_rank{rank}"
+    row_bytes = {n: (8 if t.dtype == torch.float64 else 4) * (t[0].numel() if t.dim() > 1 else 1) for n, t in arrays.items()}
+    whole = sum(t.shape[0] * row_bytes[n] for n, t in arrays.items())
+    keep = 1.0 if whole <= budget else budget / sum(t.shape[0] * (row_bytes[n] + 8) for n, t in arrays.items())
+    for i, (name, t) in enumerate(arrays.items()):
+        n = t.shape[0]
+        if keep < 1.0 and n > 0:
+            rows = np.sort(np.random.default_rng([synth.SEED, i]).choice(n, min(n, max(1, int(n * keep))), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows{sfx}.npy"), rows.astype(np.float64))
+            t = t.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=t.device))
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"),
+                t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy())
 
 
 def algorithmic_bytes(S, O, P, k, E, cov_segments=0):
@@ -66,8 +103,14 @@ def parse_args(argv=None):
                          "(tests/analytical_macro_lowering.rs:225-260, closures compiled at run time), 50k subjects x 256")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N>1: weak = --subjects per GPU; strong = one population of --subjects split N ways (BASELINE configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the oracle sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the parity sample against the CPU oracle, the CPU "
+                         "baseline, the device's write ceiling and the roofline figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one computed as DIR/<name>.npy (at most 64 MB: a "
+                         "fixed, seeded row sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the timed CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the oracle sample (--full)")
     ap.add_argument("--gather", action="store_true", help="N>1: also time the optional RCCL all-gather")
     ap.add_argument("--no-status", action="store_true", help="do not write the per-pair status bytes")
     ap.add_argument("--loglik", action="store_true",
@@ -92,7 +135,12 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal without a GPU: launch, process group (gloo), sharding, reductions and the JSON "
                          "line run, the kernel passes do not; the line carries \"dry_run\": true and value null")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the kernel passes, which --dry-run skips")
+    return args
 
 
 def launch_children(args) -> int:
@@ -455,9 +503,14 @@ def main():
         else:
             pass_ms = [evs[0].elapsed_time(evs[1]) / args.steps]
         kernel_name = runtime.last_kernel_name()
+        if args.dump_outputs:  # (before anything below touches the buffers of the last timed pass)
+            outs = {"loglik" if args.loglik else "predictions": pred}
+            if status is not None:
+                outs["status"] = status
+            dump_outputs(args.dump_outputs, outs, rank, world)
         # the device's write ceiling as measured on THIS box in THIS process (a linear streaming fill of the output buffer,
         # outside the timed region): what "attainable" means beside the 8 TB/s datasheet peak
-        if pred is not None and pred.numel() >= (1 << 22):
+        if args.full and pred is not None and pred.numel() >= (1 << 22):
             import ctypes as C
 
             from pharmsol_amd import _ffi
@@ -518,11 +571,11 @@ def main():
         except Exception as e:  # never let the optional leg kill the measured line
             gather = {"error": repr(e)[:300]}
 
-    # ---------------------------------------------------------------- parity sample + CPU baseline (rank 0)
+    # ---------------------------------------------------------------- parity sample + CPU baseline (rank 0, --full)
     cpu_baseline = None
     max_rel_err = None
     parity_ok = None
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         import oracle  # test infrastructure: the checker / the timed CPU baseline, never the product path
 
         cores = oracle.max_threads()
@@ -580,54 +633,56 @@ def main():
 
     rc = 0
     if rank == 0:
-        E_tot = flat.n_events
-        O_tot = n_obs
-        # per-launch algorithmic bytes of THIS rank's kernel (S*O = n_obs rows, S*E = n_events)
-        b_alg = 8 * O_tot * (1 if batch else P) + 8 * theta.shape[0] * k + 26 * E_tot
-        if args.loglik:  # S x P sums out, 24 B of {value, const, weight} per observation in
-            b_alg = 8 * flat.n_subjects * P + 8 * theta.shape[0] * k + 26 * E_tot + 24 * O_tot
-        # PMC counters of the same command, collected in separate rocprofv3 --pmc passes and committed (tools/pmc_run.sh,
-        # tools/kernel_counters.py): per-launch HBM traffic and vector wave-instructions of the dominant kernel
-        counters, counters_src = {}, None
-        cpath = os.path.join(ROOT, "profiles", "kernel_counters.json")
-        full_size = (world == 1 or not strong) and \
-            S_arg == {"c3": 100_000, "c2": 10_000, "c4": 50_000, "c5": 200_000, "user": 50_000}[args.workload] and \
-            P == {"c3": 1000, "c2": 1, "c4": 1, "c5": 512, "user": 256}[args.workload]
-        if full_size and os.path.exists(cpath):
-            try:
-                counters = json.load(open(cpath)).get(counters_key, {})
-                counters_src = "profiles/kernel_counters.json[%s] (%s)" % (counters_key, counters.get("source", "rocprofv3 --pmc"))
-            except Exception:
-                counters = {}
-        t_k = max(kernel_ms_mean, 1e-9) * 1e-3
-        if bound == "hbm":
-            achieved = b_alg / t_k / 1e9
-            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
-            valu = counters.get("valu_wave_insts_per_launch")
-            if valu:  # the secondary ceiling: share of the FP64 vector issue slots at the 2.4 GHz peak clock
-                roofline["valu_frac"] = valu / t_k / 1e9 / FP64_VALU_PEAK_GINST
-                roofline["valu_insts"] = valu
-            if first_alloc_ms:
-                roofline["frac_first_allocation"] = b_alg / (first_alloc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                roofline["kernel_ms_first_allocation"] = first_alloc_ms
-        else:
-            valu = counters.get("valu_wave_insts_per_launch")
-            achieved = (valu / t_k / 1e9) if valu else None
-            roofline = {"bound": "fp64_valu", "achieved": achieved, "peak": FP64_VALU_PEAK_GINST, "unit": "Gwave-inst/s",
-                        "frac": (achieved / FP64_VALU_PEAK_GINST) if achieved else None,
-                        "valu_insts": valu, "valu_source": counters_src if valu else None,
-                        "hbm_frac": b_alg / t_k / 1e9 / HBM_PEAK_GBS,
-                        "note": "compute-bound: FP64-rate vector instructions issue once per 4 cycles per SIMD; "
-                                "frac = share of the chip's issue slots at the 2.4 GHz peak clock"}
-        roofline["attainable"] = attainable_gbs if not dry else None  # measured write ceiling of this device (GB/s): linear fill
-        if attainable_gbs and roofline.get("bound") == "hbm":
-            roofline["frac_of_attainable"] = roofline["achieved"] / attainable_gbs
-        roofline.update({"traffic": counters.get("hbm_bytes_per_launch"),
-                         "traffic_source": counters_src if counters.get("hbm_bytes_per_launch") else None,
-                         "kernel": kernel_name, "kernel_ms": kernel_ms_mean, "algorithmic_bytes": b_alg})
-        if pass_ms and len(pass_ms) > 1:
-            srt = sorted(pass_ms)
-            roofline["kernel_ms_spread"] = {"min": srt[0], "median": srt[len(srt) // 2], "max": srt[-1]}
+        roofline = None
+        if args.full and not dry:
+            E_tot = flat.n_events
+            O_tot = n_obs
+            # per-launch algorithmic bytes of THIS rank's kernel (S*O = n_obs rows, S*E = n_events)
+            b_alg = 8 * O_tot * (1 if batch else P) + 8 * theta.shape[0] * k + 26 * E_tot
+            if args.loglik:  # S x P sums out, 24 B of {value, const, weight} per observation in
+                b_alg = 8 * flat.n_subjects * P + 8 * theta.shape[0] * k + 26 * E_tot + 24 * O_tot
+            # PMC counters of the same command, collected in separate rocprofv3 --pmc passes and committed (tools/pmc_run.sh,
+            # tools/kernel_counters.py): per-launch HBM traffic and vector wave-instructions of the dominant kernel
+            counters, counters_src = {}, None
+            cpath = os.path.join(ROOT, "profiles", "kernel_counters.json")
+            full_size = (world == 1 or not strong) and \
+                S_arg == {"c3": 100_000, "c2": 10_000, "c4": 50_000, "c5": 200_000, "user": 50_000}[args.workload] and \
+                P == {"c3": 1000, "c2": 1, "c4": 1, "c5": 512, "user": 256}[args.workload]
+            if full_size and os.path.exists(cpath):
+                try:
+                    counters = json.load(open(cpath)).get(counters_key, {})
+                    counters_src = "profiles/kernel_counters.json[%s] (%s)" % (counters_key, counters.get("source", "rocprofv3 --pmc"))
+                except Exception:
+                    counters = {}
+            t_k = max(kernel_ms_mean, 1e-9) * 1e-3
+            if bound == "hbm":
+                achieved = b_alg / t_k / 1e9
+                roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
+                valu = counters.get("valu_wave_insts_per_launch")
+                if valu:  # the secondary ceiling: share of the FP64 vector issue slots at the 2.4 GHz peak clock
+                    roofline["valu_frac"] = valu / t_k / 1e9 / FP64_VALU_PEAK_GINST
+                    roofline["valu_insts"] = valu
+                if first_alloc_ms:
+                    roofline["frac_first_allocation"] = b_alg / (first_alloc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                    roofline["kernel_ms_first_allocation"] = first_alloc_ms
+            else:
+                valu = counters.get("valu_wave_insts_per_launch")
+                achieved = (valu / t_k / 1e9) if valu else None
+                roofline = {"bound": "fp64_valu", "achieved": achieved, "peak": FP64_VALU_PEAK_GINST, "unit": "Gwave-inst/s",
+                            "frac": (achieved / FP64_VALU_PEAK_GINST) if achieved else None,
+                            "valu_insts": valu, "valu_source": counters_src if valu else None,
+                            "hbm_frac": b_alg / t_k / 1e9 / HBM_PEAK_GBS,
+                            "note": "compute-bound: FP64-rate vector instructions issue once per 4 cycles per SIMD; "
+                                    "frac = share of the chip's issue slots at the 2.4 GHz peak clock"}
+            roofline["attainable"] = attainable_gbs if not dry else None  # measured write ceiling of this device (GB/s): linear fill
+            if attainable_gbs and roofline.get("bound") == "hbm":
+                roofline["frac_of_attainable"] = roofline["achieved"] / attainable_gbs
+            roofline.update({"traffic": counters.get("hbm_bytes_per_launch"),
+                             "traffic_source": counters_src if counters.get("hbm_bytes_per_launch") else None,
+                             "kernel": kernel_name, "kernel_ms": kernel_ms_mean, "algorithmic_bytes": b_alg})
+            if pass_ms and len(pass_ms) > 1:
+                srt = sorted(pass_ms)
+                roofline["kernel_ms_spread"] = {"min": srt[0], "median": srt[len(srt) // 2], "max": srt[-1]}
         value = (steps_per_pass * args.steps / elapsed_max) if not dry else None
         line = {
             "metric": "subject_event_steps_per_sec", "value": value, "unit": "subject-event-steps/s",

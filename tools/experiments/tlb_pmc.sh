@@ -8,7 +8,7 @@ mkdir -p $OUT
 for mode in first best; do
   extra="--alloc-tries 1"; [ $mode = best ] && extra="--place-gib 1 --alloc-tries 8"
   timeout -k 10 150 rocprofv3 --pmc TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_REQUEST_sum \
-    --output-format csv -d $OUT/$mode -o pmc -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --place-gib 0 $extra > $OUT/$mode.json 2> $OUT/$mode.err
+    --output-format csv -d $OUT/$mode -o pmc -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --place-gib 0 $extra > $OUT/$mode.json 2> $OUT/$mode.err
   echo "$mode rc=$?"
   python3 - $OUT/$mode <<'PY'
 import csv, glob, sys, collections
