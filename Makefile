@@ -7,7 +7,7 @@ LIB := pharmsol_amd/lib/libpmx_hip.so
 # lines (slope*t + intercept) exactly like the reference; device code keeps FMA contraction.
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
-OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_kernels.o $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
+OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(CSRC)/build/pmx_kernels.o $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 
 all: $(LIB) oracle
@@ -16,7 +16,9 @@ $(CSRC)/build/pmx_compile.o: $(CSRC)/pmx_compile.cpp $(CSRC)/pmx_compile.hpp $(C
 	@mkdir -p $(CSRC)/build
 	g++ $(HOSTFLAGS) -c $< -o $@
 
-$(CSRC)/build/pmx_api.o: $(CSRC)/pmx_api.cpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_jit.hpp $(DEVHDR)
+# the C ABI's translation units (pmx_internal.hpp): entry points, device streams, launch path
+APIHDR := $(CSRC)/pmx_internal.hpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_jit.hpp $(DEVHDR)
+$(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o: $(CSRC)/build/%.o: $(CSRC)/%.cpp $(APIHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -x hip -c $< -o $@
 

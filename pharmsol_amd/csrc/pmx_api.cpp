@@ -2,24 +2,12 @@
 //
 // No CPU compute path exists in this library: if there is no HIP device the
 // entry points fail with PMX_ERR_NO_DEVICE.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <limits>
-#include <memory>
-#include <map>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/pmx.h"
-#include "pmx_compile.hpp"
-#include "pmx_jit.hpp"
-#include <dlfcn.h>
-#include "pmx_kernels.hpp"
+#include "pmx_internal.hpp"
 #include "pmx_structures.hpp"  // kernel_nparams()
 
 namespace {
@@ -27,143 +15,7 @@ namespace {
 thread_local std::string g_err;
 thread_local const char* g_kernel_name = "";
 
-int32_t fail(int32_t code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
 int32_t create_user_ode(const pmx_model_desc* d, const char* source, uint32_t fns, pmx_model** out);  // (after check_user_ode)
-
-// Developer switches (INTEGRATION.md "environment switches").  Read ONCE, at the first call that needs them: a
-// std::getenv per launch is measurable on the 11 us C2 pass.  pmx_debug_reload_env() re-reads them (tuning scripts
-// and tests that flip a switch inside one process).
-struct Tunables {
-  bool disable_ladder = false, disable_classing = false, ll_old = false;
-  int32_t steps_per_trip = 0, grid_min_p = 0, min_class = 0, cpb = 0;
-  int32_t spread = -1, loose = -1;  // -1 = library default
-  int32_t prop_slots = -1, dyn_tile = 0;
-  void load() {
-    auto flag = [](const char* n) {
-      const char* e = std::getenv(n);
-      return e && e[0] && e[0] != '0';
-    };
-    auto num = [](const char* n) {
-      const char* e = std::getenv(n);
-      const int v = e ? std::atoi(e) : 0;
-      return v > 0 ? v : 0;
-    };
-    auto tri = [](const char* n) {
-      const char* e = std::getenv(n);
-      return e ? ((e[0] && e[0] != '0') ? 1 : 0) : -1;
-    };
-    disable_ladder = flag("PMX_DISABLE_LADDER");
-    disable_classing = flag("PMX_DISABLE_CLASSING");
-    ll_old = flag("PMX_TUNE_LL_OLD");
-    steps_per_trip = num("PMX_TUNE_STEPS_PER_TRIP");
-    grid_min_p = num("PMX_TUNE_GRID_MIN_P");
-    min_class = num("PMX_TUNE_MIN_CLASS");
-    cpb = num("PMX_TUNE_CPB");
-    {
-      const char* e = std::getenv("PMX_TUNE_PROP_SLOTS");
-      prop_slots = e ? std::atoi(e) : -1;
-    }
-    dyn_tile = num("PMX_TUNE_DYN_TILE");
-    spread = tri("PMX_TUNE_SPREAD");
-    loose = tri("PMX_TUNE_LOOSE");
-  }
-};
-std::mutex g_tun_mu;
-Tunables g_tun;
-bool g_tun_loaded = false;
-Tunables tunables() {
-  std::lock_guard<std::mutex> lock(g_tun_mu);
-  if (!g_tun_loaded) {
-    g_tun.load();
-    g_tun_loaded = true;
-  }
-  return g_tun;
-}
-
-#define PMX_HIP(call)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(e_ == hipErrorOutOfMemory ? PMX_ERR_OUT_OF_MEMORY : PMX_ERR_HIP,                 \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                              \
-  } while (0)
-
-// Restores the caller's current device on scope exit.
-struct DeviceGuard {
-  int prev = -1;
-  bool active = false;
-  hipError_t enter(int dev) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev != dev) {
-      e = hipSetDevice(dev);
-      active = (e == hipSuccess);
-    }
-    return e;
-  }
-  ~DeviceGuard() {
-    if (active) (void)hipSetDevice(prev);
-  }
-};
-
-struct DeviceStream {
-  pmx::CompileKey key;
-  pmx::DevOps dev{};
-  pmx::DevClassPlan cls{};
-  pmx::DevSteps steps{};  // fused step programs of the lean generic walker (analytical streams without lag / covariates)
-  int64_t n_classed_subjects = 0;
-  // host copies for the log-likelihood's per-chunk observation blocks
-  std::vector<int64_t> h_chunk_row;      // [n_chunks*G]
-  std::vector<int32_t> h_chunk_nobs;     // [n_chunks] observations per member of the chunk's class
-  std::vector<int32_t> h_chunk_n;        // [n_chunks] live members
-  // Sigma tables of the log-likelihood, per set of error models.  They are filled ON THE DEVICE
-  // (pmx_kernels.hip pmx_ll_prepare_*), stream-ordered before the kernel that reads them: an optimiser that changes
-  // gamma / lambda every call pays two ~10 us kernels, not a host pass over every observation plus a 40 MB upload.
-  // A small LRU of slots; uses of one slot are chained through its event so that a slot is never rewritten while a
-  // kernel on another stream still reads it.
-  struct LLCache {
-    std::vector<pmx_error_model> em;
-    double* d_obs = nullptr;   // [n_obs][4]
-    double* d_cobs = nullptr;  // classed blocks
-    int32_t* d_err = nullptr;  // invalid-sigma counter of the last fill
-    hipEvent_t ev = nullptr;   // last use (fill or read) of this slot
-    int64_t stamp = 0;         // LRU
-    int32_t host_users = 0;    // host threads between "picked" and "launched"
-  };
-  std::deque<LLCache> ll_cache;  // (deque: slots handed out by pointer must survive later push_backs)
-  int64_t ll_stamp = 0;
-  const int32_t* d_chunk_nobs = nullptr;     // [n_chunks]
-  const int64_t* d_chunk_obs_off = nullptr;  // [n_chunks] offsets into a slot's cobs
-  int64_t cobs_size = 0;
-  std::vector<void*> allocs;
-  int32_t max_input_used = -1;
-  int64_t n_ops = 0, n_prop = 0;
-  int64_t max_lagb_per_list = 0;
-  int32_t prop_cache_used = 0;        // LDS slots the stream's propagator-cache codes use
-  bool no_rates = false;              // no PROP of the stream has an active infusion
-  bool eig_reuse = false;             // some PROP repeats the previous built segment's covariate factor row (bit 27)
-  double prop_reuse_fraction = 0.0;   // share of PROP ops that take a kept propagator
-  ~DeviceStream() {
-    for (void* p : allocs) (void)hipFree(p);
-    for (auto& c : ll_cache)
-      if (c.ev) (void)hipEventDestroy(c.ev);
-  }
-};
-
-template <class T>
-int32_t upload(const std::vector<T>& v, const T** out, std::vector<void*>* allocs) {
-  *out = nullptr;
-  if (v.empty()) return PMX_OK;
-  void* p = nullptr;
-  PMX_HIP(hipMalloc(&p, v.size() * sizeof(T)));
-  allocs->push_back(p);
-  PMX_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<const T*>(p);
-  return PMX_OK;
-}
 
 int ode_nstates(int model) {
   static const int n[PMX_ODE_MODEL_COUNT] = {1, 2, 2, 3, 3, 4, 1};
@@ -174,11 +26,22 @@ int ode_nparams(int model) {
   return (model >= 0 && model < PMX_ODE_MODEL_COUNT) ? n[model] : -1;
 }
 
+// every pmx_model_create* ends here: the model's device-side description is fixed from now on
+int32_t publish(std::unique_ptr<pmx_model>& m, pmx_model** out) {
+  finish_model(m.get());
+  *out = m.release();
+  return PMX_OK;
+}
+
 }  // namespace
 
 namespace pmx {
-// the calling thread's error text, for the other translation units of the C ABI (pmx_shard.cpp)
-int32_t set_error(int32_t code, const std::string& msg) { return fail(code, msg); }
+// the calling thread's error text / kernel name, for the other translation units of the C ABI
+int32_t set_error(int32_t code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+void set_kernel_name(const char* name) { g_kernel_name = name; }
 }  // namespace pmx
 
 // What the HOST-pointer entry points (pmx_predict, pmx_predict_batch, pmx_loglik, pmx_loglik_batch) keep between
@@ -212,47 +75,10 @@ struct HostWorkspace {
   }
 };
 
-struct pmx_population {
-  int device = 0;
-  pmx::HostPopulation hp;
-  std::mutex mu;
-  std::unique_ptr<HostWorkspace> ws;  // created by the first host-pointer call
-  // what the log-likelihood tables are computed from, uploaded at the first pmx_loglik* call
-  bool ll_ready = false;
-  const double* d_obs_y = nullptr;
-  const int32_t* d_obs_outeq = nullptr;
-  const double* d_obs_poly = nullptr;
-  const int8_t* d_obs_cens = nullptr;
-  uint32_t valued_outeq_mask = 0;  // bit q: some observation on output q carries a value
-  bool any_censored = false;
-  std::vector<void*> ll_allocs;
-  ~pmx_population() {
-    for (void* p : ll_allocs) (void)hipFree(p);
-  }
-  std::vector<std::unique_ptr<DeviceStream>> streams;  // one per model flavour, built lazily
-};
-
-struct pmx_model {
-  pmx_model_desc d;
-  bool dyn = false;  // kernel parameters depend on covariates
-  bool has_init = false;
-  // custom (hiprtc) models: the code object and its per-device modules
-  bool custom = false;
-  uint32_t user_fns = 0;  // PMX_FN_* the user's source defines (pmx_model_create_user)
-  bool user_lag = false, user_eq = false;  // user model: any lag closure (user's or descriptor's) / own propagator
-  bool user_ode = false;                   // ODE model on the general walker (pmx_ode_user.hpp): lag / fa / derive closures, bolus[]
-  std::vector<char> jit_code;
-  pmx::JitSpec jit_spec;  // what jit_code was compiled from (the big-lists build below is made from it on demand)
-  mutable std::vector<char> jit_code_big;  // closure walkers: the PMX_USER_BIG_LISTS build, compiled at the first launch on a
-                                           // population with more than 64 lagged boluses in one occasion (pmx_userlag.hpp)
-  mutable std::mutex jit_mu;
-  mutable std::map<int, pmx::JitModule> jit_modules;
-  mutable std::map<int, pmx::JitModule> jit_modules_big;
-  ~pmx_model() {
-    for (auto& kv : jit_modules) pmx::jit_unload(&kv.second);
-    for (auto& kv : jit_modules_big) pmx::jit_unload(&kv.second);
-  }
-};
+pmx_population::pmx_population() = default;
+pmx_population::~pmx_population() {
+  for (void* p : ll_allocs) (void)hipFree(p);
+}
 
 extern "C" {
 
@@ -283,11 +109,7 @@ int32_t pmx_device_count(void) {
 
 const char* pmx_last_error(void) { return g_err.c_str(); }
 
-void pmx_debug_reload_env(void) {
-  std::lock_guard<std::mutex> lock(g_tun_mu);
-  g_tun.load();
-  g_tun_loaded = true;
-}
+void pmx_debug_reload_env(void) { pmx::reload_tunables(); }
 const char* pmx_last_kernel_name(void) { return g_kernel_name; }
 
 int32_t pmx_population_create(const pmx_population_desc* desc, int32_t device, pmx_population** out) {
@@ -525,8 +347,7 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     m->d = dd;
     m->custom = true;
   }
-  *out = m.release();
-  return PMX_OK;
+  return publish(m, out);
 }
 
 }  // extern "C"
@@ -594,8 +415,7 @@ int32_t pmx_model_create_custom(const pmx_model_desc* d, const char* source, int
   m->jit_spec = spec_of(d, source, has_init);
   if (!pmx::jit_compile(m->jit_spec, &m->jit_code, &log))
     return fail(PMX_ERR_INVALID_ARGUMENT, "hiprtc could not compile the model source:\n" + log);
-  *out = m.release();
-  return PMX_OK;
+  return publish(m, out);
 }
 
 int32_t pmx_debug_jit_source(const pmx_model_desc* d, const char* source, int32_t has_init, char** out_text) {
@@ -716,8 +536,7 @@ int32_t create_user_ode(const pmx_model_desc* d, const char* source, uint32_t fn
   m->jit_spec = user_spec_of(d, source, fns);
   if (!pmx::jit_compile(m->jit_spec, &m->jit_code, &log))
     return fail(PMX_ERR_INVALID_ARGUMENT, "hiprtc could not compile the model source:\n" + log);
-  *out = m.release();
-  return PMX_OK;
+  return publish(m, out);
 }
 }  // namespace
 
@@ -748,8 +567,7 @@ int32_t pmx_model_create_user(const pmx_model_desc* d, const char* source, uint3
   m->jit_spec = user_spec_of(d, source, functions);
   if (!pmx::jit_compile(m->jit_spec, &m->jit_code, &log))
     return fail(PMX_ERR_INVALID_ARGUMENT, "hiprtc could not compile the model source:\n" + log);
-  *out = m.release();
-  return PMX_OK;
+  return publish(m, out);
 }
 
 int32_t pmx_debug_jit_source_user(const pmx_model_desc* d, const char* source, uint32_t functions, char** out_text) {
@@ -775,649 +593,6 @@ void pmx_model_destroy(pmx_model* m) { delete m; }
 }  // extern "C"
 
 namespace {
-
-pmx::CompileKey key_for(const pmx_model* m) {
-  pmx::CompileKey k;
-  k.eq_kind = m->d.eq_kind;
-  if (m->d.eq_kind == PMX_EQ_ANALYTICAL && m->custom) {
-    // user closures (pmx_analytical.hpp): covariates are looked up on the device, so the stream carries no factors;
-    // absolute times on every PROP, solve marks for seq_eq, every input's rate for a user propagator, and - when the
-    // model has any lag closure - ALL boluses leave the stream into one list per occasion that each lane sorts itself
-    k.cov_time_mode = PMX_COV_TIME_SEGMENT_DT;  // (unused: no host-side covariate evaluation)
-    k.rk4_h_max = 0.0;
-    k.rate_input = (m->d.pmetrics_indexing && !m->user_eq) ? 1 : 0;  // (pm_* wrappers read rateiv[1]: analytical/mod.rs:86-88)
-    k.full_rates = m->user_eq;
-    k.n_rate = m->user_eq ? (m->d.ndrugs > 0 ? m->d.ndrugs : 1) : 1;
-    k.want_times = true;
-    k.solve_marks = true;
-    k.user_cov = true;
-    if (m->user_lag) {
-      k.lag_merge = true;
-      for (int i = 0; i < m->d.ndrugs && i < PMX_MAX_INPUTS; ++i) k.lag_mask |= (1u << i);
-    }
-  } else if (m->d.eq_kind == PMX_EQ_ANALYTICAL) {
-    k.cov_time_mode = m->d.cov_time_mode;
-    k.rk4_h_max = 0.0;
-    k.n_rate = 1;
-    k.rate_input = m->d.pmetrics_indexing ? 1 : 0;
-    // classed fast path: theta-only coefficients, no covariates, plain indexing
-    for (int i = 0; i < PMX_MAX_INPUTS; ++i)
-      if (m->d.lag_param[i] >= 0) k.lag_mask |= (1u << i);
-    // (bioavailability does not stop classing: the amounts in the plan are the recorded ones, each lane scales them)
-    const Tunables tun = tunables();
-    k.ladder = !m->dyn && k.lag_mask == 0 && !tun.disable_ladder;  // (switch: fresh exp() on every step, A/B and parity checks)
-    k.n_derived = m->d.n_derived;
-    std::memcpy(k.derived, m->d.derived, sizeof(k.derived));
-    const bool disabled = tun.disable_classing;
-    bool reads_pad = false;  // pm_ indexing: an output on model state 0 reads the wrapper's pad slot (generic walker only)
-    if (m->d.pmetrics_indexing)
-      for (int o = 0; o < m->d.nout && o < PMX_MAX_OUT; ++o)
-        if (m->d.out[o].state == 0) reads_pad = true;
-    // (one lagged input is classed too: in an exact class the bolus times are shared, so a lane's split points and the
-    // propagator of every sub-interval serve all G members)
-    const bool lag_ok = (k.lag_mask & (k.lag_mask - 1u)) == 0u;
-    // (covariate-derived constants are classed by program shape alone, each member with its own factor rows)
-    const bool plain = !m->dyn && m->d.n_covariates == 0;
-    // ... where it pays: the one- and two-state structures (1-cpt + absorption 3.41 -> 2.87 ms on the C5 design); from
-    // three states up the rebuild is so dominated by its own arithmetic that the batch gains nothing (C5: 19.4 -> 19.9 ms)
-    const int st = pmx::kernel_structure(m->d.kernel);
-    const bool dyn_ok = m->dyn && !m->d.pmetrics_indexing && k.lag_mask == 0 &&
-                        (st == pmx::S_ONE || st == pmx::S_ONE_ABS || st == pmx::S_TWO);
-    if (!disabled && !reads_pad && lag_ok && (plain || dyn_ok)) {
-      k.class_g = (st == pmx::S_ONE || st == pmx::S_ONE_ABS || st == pmx::S_TWO) ? 8 : 4;  // == ClassBatch<KID>::G
-    }
-    // covariate models that take the generic walker: equal (length, factors) PROPs of an occasion share a propagator
-    if (m->dyn && k.lag_mask == 0 && k.class_g == 0 && (st == pmx::S_THREE || st == pmx::S_THREE_ABS) && !m->d.pmetrics_indexing) {
-      k.kfac_n = pmx::kernel_nparams(m->d.kernel);  // (the matrix-free walker, pmx_analytical_dyn3)
-      for (int j = 0; j < k.kfac_n && j < 8; ++j)
-        k.kfac_map[j] = (m->d.n_bind > 0 && m->d.bind[j].src == PMX_SRC_DERIVED) ? static_cast<int8_t>(m->d.bind[j].index) : int8_t(-1);
-    }
-    if (m->dyn && k.lag_mask == 0 && k.class_g == 0) {
-      k.prop_cache_slots = tun.prop_slots >= 0 ? (tun.prop_slots > 3 ? 3 : tun.prop_slots) : 1;
-      // the kept propagators live in LDS, [slot][component][256 lanes]: stay inside the 64 KB a block may take without an
-      // opt-in attribute (the stream's cache codes are written for THIS number of slots, so it is fixed here)
-      static const int kPropDoubles[6] = {2, 4, 6, 9, 12, 16};  // sizeof(Structure<ST>::Prop) / 8, ST = S_ONE .. S_THREE_ABS
-      const int per_slot = kPropDoubles[st] * 8 * 256;
-      while (k.prop_cache_slots > 0 && k.prop_cache_slots * per_slot > (64 << 10)) --k.prop_cache_slots;
-    }  // (one slot: a second costs more occupancy
-    // than its extra reuse returns - C5: 1 slot 16.8 ms, 2 slots 19.4 ms, none 20.2 ms; tools/c5 notes in DESIGN.md)
-  } else if (m->user_ode) {
-    // ODE with user lag / fa / derive closures (pmx_ode_user.hpp): covariates are looked up on the device, every PROP
-    // carries its absolute [t0, t1), every input's rate rides along, and - when the model has any lag closure - ALL
-    // boluses leave the stream into one list per occasion that each lane sorts itself
-    k.cov_time_mode = PMX_COV_TIME_SEGMENT_END_ABS;
-    k.rk4_h_max = m->d.rk4_h_max;
-    k.n_rate = m->d.ndrugs > 0 ? m->d.ndrugs : 1;
-    k.rate_input = 0;
-    k.want_times = true;
-    k.user_cov = true;
-    if (m->user_lag) {
-      k.lag_merge = true;
-      for (int i = 0; i < m->d.ndrugs && i < PMX_MAX_INPUTS; ++i) k.lag_mask |= (1u << i);
-    }
-  } else {
-    k.cov_time_mode = PMX_COV_TIME_SEGMENT_END_ABS;
-    k.rk4_h_max = m->d.rk4_h_max;
-    k.n_rate = m->d.ndrugs > 0 ? m->d.ndrugs : 1;
-    k.rate_input = 0;
-    for (int i = 0; i < PMX_MAX_INPUTS; ++i)
-      if (m->d.lag_param[i] >= 0) k.lag_mask |= (1u << i);
-    // absolute piece times: a user body may be non-autonomous; the adaptive solver steps on [t0, t1] itself
-    k.want_times = m->custom || m->d.ode_solver != PMX_SOLVER_RK4;
-  }
-  return k;
-}
-
-// Find or build (compile + upload) the device op stream for this model flavour.
-int32_t get_stream(pmx_population* pop, const pmx::CompileKey& key_in, DeviceStream** out) {
-  std::lock_guard<std::mutex> lock(pop->mu);
-  pmx::CompileKey key = key_in;
-  if (key.kfac_n > 0 && key.prop_cache_slots == 1 && tunables().prop_slots < 0 && std::getenv("PMX_DISABLE_DYN3") == nullptr) {
-    // a population without infusions takes the matrix-free walker, whose kept segment is 6-7 numbers per lane: two slots
-    // fit where the matrix form held one (C5: 8 rebuilds per subject instead of 9)
-    bool infusions = false;
-    for (uint8_t kd : pop->hp.ev_kind) infusions |= (kd == PMX_EV_INFUSION);
-    if (!infusions) key.prop_cache_slots = 2;
-  }
-  for (auto& s : pop->streams)
-    if (s->key == key) {
-      *out = s.get();
-      return PMX_OK;
-    }
-  pmx::OpStream os;
-  std::string err;
-  int32_t rc = pmx::compile_ops(pop->hp, key, &os, &err);
-  if (rc != PMX_OK) return fail(rc, err);
-  auto ds = std::make_unique<DeviceStream>();
-  ds->key = key;
-  ds->max_input_used = os.max_input_used;
-  ds->n_ops = os.n_ops;
-  ds->n_prop = os.n_prop;
-  if ((rc = upload(os.subj_op_off, &ds->dev.subj_op_off, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(pop->hp.subj_obs_off, &ds->dev.subj_obs_off, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.subj_order, &ds->dev.subj_order, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_meta, &ds->dev.op_meta, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_a, &ds->dev.op_a, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_b, &ds->dev.op_b, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_n, &ds->dev.op_n, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_rate, &ds->dev.op_rate, &ds->allocs)) != PMX_OK) return rc;
-  if (key.eq_kind == PMX_EQ_ODE) {  // packed per-op records (pmx_devtypes.hpp DevOps::op_rec)
-    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 6, 0.0);
-    const bool times = !os.op_t0.empty();
-    for (int64_t o = 0; o < os.n_ops; ++o) {
-      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]) | (static_cast<uint64_t>(static_cast<uint32_t>(os.op_n[o])) << 32);
-      std::memcpy(&rec[6 * o], &w, 8);
-      rec[6 * o + 1] = os.op_a[o];
-      rec[6 * o + 2] = os.op_b[o];
-      rec[6 * o + 3] = key.n_rate > 0 ? os.op_rate[o * key.n_rate] : 0.0;
-      rec[6 * o + 4] = times ? os.op_t0[o] : 0.0;
-      rec[6 * o + 5] = times ? os.op_t1[o] : 0.0;
-    }
-    if ((rc = upload(rec, &ds->dev.op_rec, &ds->allocs)) != PMX_OK) return rc;
-  } else {  // analytical: {meta (bits), a, b, t0} = 32 bytes
-    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 4, 0.0);
-    const bool times = !os.op_t0.empty();
-    for (int64_t o = 0; o < os.n_ops; ++o) {
-      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]);
-      std::memcpy(&rec[4 * o], &w, 8);
-      rec[4 * o + 1] = os.op_a[o];
-      rec[4 * o + 2] = os.op_b[o];
-      rec[4 * o + 3] = times ? os.op_t0[o] : 0.0;
-    }
-    if ((rc = upload(rec, &ds->dev.op_rec, &ds->allocs)) != PMX_OK) return rc;
-  }
-  if ((rc = upload(os.op_fac, &ds->dev.op_fac, &ds->allocs)) != PMX_OK) return rc;
-  if (key.kfac_n > 0 && !os.op_fac.empty()) {  // one 64-byte record per op for the matrix-free walker (DevOps::op_kfac)
-    const size_t n_ops = os.op_meta.size();
-    const size_t fw = static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS;
-    std::vector<double> kf(n_ops * 8, 1.0);
-    for (size_t o = 0; o < n_ops; ++o) {
-      for (int j = 0; j < key.kfac_n && j < 7; ++j) {
-        const int dd = key.kfac_map[j];
-        if (dd < 0 || dd >= key.n_derived) continue;
-        double f = 1.0;  // the parameter's factors multiplied out: theta * (f0 * f1) for the descriptor's (theta * f0) * f1
-        for (int q = 0; q < key.derived[dd].n_factors && q < PMX_MAX_FACTORS; ++q) f *= os.op_fac[o * fw + static_cast<size_t>(dd) * PMX_MAX_FACTORS + q];
-        kf[o * 8 + j] = f;
-      }
-      kf[o * 8 + 7] = os.op_a[o];
-    }
-    if ((rc = upload(kf, &ds->dev.op_kfac, &ds->allocs)) != PMX_OK) return rc;
-  }
-  if ((rc = upload(os.op_t0, &ds->dev.op_t0, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.op_t1, &ds->dev.op_t1, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.lagb_off, &ds->dev.lagb_off, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.lagb_time, &ds->dev.lagb_time, &ds->allocs)) != PMX_OK) return rc;
-  if ((rc = upload(os.lagb_amount, &ds->dev.lagb_amount, &ds->allocs)) != PMX_OK) return rc;
-  if (key.lag_merge && (rc = upload(os.lagb_input, &ds->dev.lagb_input, &ds->allocs)) != PMX_OK) return rc;
-  ds->max_lagb_per_list = os.max_lagb_per_list;
-  ds->prop_cache_used = os.prop_cache_used;
-  ds->no_rates = true;  // (analytical streams: a PROP's op_b is its rate)
-  for (size_t o = 0; o < os.op_meta.size() && ds->no_rates; ++o)
-    if ((os.op_meta[o] & 0xffu) == pmx::OP_PROP && os.op_b[o] != 0.0) ds->no_rates = false;
-  ds->eig_reuse = false;  // (covariate streams: bit 27 of a PROP = "same rate constants as the previous built segment")
-  if (key.prop_cache_slots > 0 && !os.op_fac.empty())
-    for (size_t o = 0; o < os.op_meta.size() && !ds->eig_reuse; ++o)
-      if ((os.op_meta[o] & 0xffu) == pmx::OP_PROP && (os.op_meta[o] & (1u << 27))) ds->eig_reuse = true;
-  ds->prop_reuse_fraction = os.n_prop > 0 ? static_cast<double>(os.n_prop_reused) / static_cast<double>(os.n_prop) : 0.0;
-  ds->dev.n_rate = key.n_rate;
-  ds->dev.n_cov = 0;
-  if ((key.eq_kind == PMX_EQ_ODE || key.user_cov) && pop->hp.n_cov > 0) {  // covariate segments for bodies that read them on the device
-    const auto& hp = pop->hp;
-    ds->dev.n_cov = hp.n_cov;
-    if ((rc = upload(hp.cov_seg_off, &ds->dev.cov_seg_off, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.seg_from, &ds->dev.seg_from, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.seg_to, &ds->dev.seg_to, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.seg_slope, &ds->dev.seg_slope, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.seg_icpt, &ds->dev.seg_icpt, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.cov_first_t, &ds->dev.cov_first_t, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.cov_first_v, &ds->dev.cov_first_v, &ds->allocs)) != PMX_OK) return rc;
-  }
-  if (key.eq_kind == PMX_EQ_ANALYTICAL && !key.user_cov && key.lag_mask == 0 && os.op_fac.empty()) {
-    std::vector<int64_t> off;
-    std::vector<double> rec;
-    pmx::build_step_stream(os, &off, &rec);
-    if ((rc = upload(off, &ds->steps.subj_step_off, &ds->allocs)) != PMX_OK) return rc;
-    if ((rc = upload(rec, &ds->steps.step_rec, &ds->allocs)) != PMX_OK) return rc;
-  }
-  if (key.class_g > 0) {
-    pmx::ClassPlan cp;
-    const Tunables tun = tunables();  // (tuning experiments)
-    const int32_t min_class = tun.min_class > 0 ? tun.min_class : key.class_g / 2;
-    const bool spread = tun.spread < 0 ? true : tun.spread != 0;  // (0.94-0.97 vs 1.05-1.11 ms on C3 in most allocations, never slower: tools/experiments/alloc_tune.py)
-    const bool loose = tun.loose < 0 ? true : tun.loose != 0;  // subjects without a shared design still share a program shape: batched with per-member step lengths
-    pmx::build_class_plan(pop->hp, os, key.class_g, min_class, &cp, key.ladder, spread, loose);
-    if (cp.n_chunks > 0) {
-      if ((rc = upload(cp.prog_meta, &ds->cls.prog_meta, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.prog_dt, &ds->cls.prog_dt, &ds->allocs)) != PMX_OK) return rc;
-      {
-        std::vector<double> prec((cp.prog_meta.size() + 1) * 2, 0.0);
-        for (size_t i = 0; i < cp.prog_meta.size(); ++i) {
-          const uint64_t w = cp.prog_meta[i];
-          std::memcpy(&prec[2 * i], &w, 8);
-          prec[2 * i + 1] = cp.prog_dt[i];
-        }
-        if ((rc = upload(prec, &ds->cls.prog_rec, &ds->allocs)) != PMX_OK) return rc;
-        if ((rc = upload(cp.chunk_rate_mask, &ds->cls.chunk_rate_mask, &ds->allocs)) != PMX_OK) return rc;
-        if ((rc = upload(cp.cls_fast_mask, &ds->cls.cls_fast_mask, &ds->allocs)) != PMX_OK) return rc;
-      }
-      if ((rc = upload(cp.prog_t0, &ds->cls.prog_t0, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.prog_t1, &ds->cls.prog_t1, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.cls_prog_off, &ds->cls.cls_prog_off, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.chunk_cls, &ds->cls.chunk_cls, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.chunk_n, &ds->cls.chunk_n, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.chunk_val_off, &ds->cls.chunk_val_off, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.chunk_subj, &ds->cls.chunk_subj, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.chunk_row, &ds->cls.chunk_row, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.val, &ds->cls.val, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.dtv, &ds->cls.dtv, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.facp, &ds->cls.facp, &ds->allocs)) != PMX_OK) return rc;
-      if ((rc = upload(cp.faco, &ds->cls.faco, &ds->allocs)) != PMX_OK) return rc;
-      ds->cls.n_fac = cp.n_fac;
-      if ((rc = upload(cp.generic_subjects, &ds->cls.generic_subjects, &ds->allocs)) != PMX_OK) return rc;
-      ds->h_chunk_row = cp.chunk_row;
-      ds->h_chunk_n = cp.chunk_n;
-      ds->h_chunk_nobs.resize(static_cast<size_t>(cp.n_chunks));
-      for (int64_t c = 0; c < cp.n_chunks; ++c) {
-        const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
-        int32_t nobs = 0;
-        for (int64_t o = cp.cls_prog_off[cl]; o < cp.cls_prog_off[cl + 1]; ++o) nobs += (cp.prog_meta[static_cast<size_t>(o)] >> 24) & 1u;
-        ds->h_chunk_nobs[static_cast<size_t>(c)] = nobs;
-      }
-      {  // where each chunk's block {[G] constant sums, [G] flags, [observation][value|weight][G]} starts in a slot's cobs
-        std::vector<int64_t> off(static_cast<size_t>(cp.n_chunks) + 1);
-        int64_t at = 0;
-        for (int64_t c = 0; c < cp.n_chunks; ++c) {
-          off[static_cast<size_t>(c)] = at;
-          at += (static_cast<int64_t>(ds->h_chunk_nobs[static_cast<size_t>(c)]) * 2 + 2) * cp.G;
-        }
-        off[static_cast<size_t>(cp.n_chunks)] = at;  // sentinel
-        ds->cobs_size = at;
-        if ((rc = upload(ds->h_chunk_nobs, &ds->d_chunk_nobs, &ds->allocs)) != PMX_OK) return rc;
-        if ((rc = upload(off, &ds->d_chunk_obs_off, &ds->allocs)) != PMX_OK) return rc;
-        {
-          // one 64-byte record per chunk for pmx_analytical_classed_ll (pmx_kernels.hpp DevClassPlan::chunk_hdr): everything
-          // the kernel needs of a chunk in ONE scalar fetch.  32-bit offsets and 16-bit counts: a plan outside those
-          // limits simply keeps the round-2 kernel (chunk_hdr stays null).
-          bool fits = cp.G <= 8 && at < (int64_t{1} << 32) && static_cast<int64_t>(cp.val.size()) < (int64_t{1} << 32) &&
-                      static_cast<int64_t>(cp.prog_meta.size()) < (int64_t{1} << 32);
-          for (size_t cl = 0; cl + 1 < cp.cls_prog_off.size() && fits; ++cl)
-            fits = cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl] < 65536;
-          if (fits) {
-            std::vector<uint32_t> hdr((static_cast<size_t>(cp.n_chunks) + 1) * 16, 0);
-            for (int64_t c = 0; c < cp.n_chunks; ++c) {
-              uint32_t* q = &hdr[static_cast<size_t>(c) * 16];
-              const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
-              q[0] = static_cast<uint32_t>(cp.chunk_n[static_cast<size_t>(c)]) |
-                     (static_cast<uint32_t>(cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl]) << 16);
-              q[1] = static_cast<uint32_t>(cp.cls_prog_off[cl]);
-              q[2] = static_cast<uint32_t>(cp.chunk_val_off[static_cast<size_t>(c)]);
-              q[3] = static_cast<uint32_t>(off[static_cast<size_t>(c)]);
-              const uint64_t rm = cp.chunk_rate_mask[static_cast<size_t>(c)], fm = cp.cls_fast_mask[cl];
-              q[4] = static_cast<uint32_t>(rm);
-              q[5] = static_cast<uint32_t>(rm >> 32);
-              q[6] = static_cast<uint32_t>(fm);
-              q[7] = static_cast<uint32_t>(fm >> 32);
-              for (int32_t j = 0; j < cp.G; ++j) q[8 + j] = static_cast<uint32_t>(cp.chunk_subj[static_cast<size_t>(c) * cp.G + j]);
-            }
-            const uint32_t* d_hdr = nullptr;
-            if ((rc = upload(hdr, &d_hdr, &ds->allocs)) != PMX_OK) return rc;
-            ds->cls.chunk_hdr = d_hdr;
-          }
-        }
-      }
-      ds->cls.n_chunks = cp.n_chunks;
-      ds->cls.n_chunks_exact = cp.n_chunks_exact;
-      ds->cls.n_generic = static_cast<int64_t>(cp.generic_subjects.size());
-      ds->cls.G = cp.G;
-      ds->n_classed_subjects = cp.n_classed_subjects;
-    }
-  }
-  *out = ds.get();
-  pop->streams.push_back(std::move(ds));
-  return PMX_OK;
-}
-
-// Pick (or fill) the slot holding the sigma tables for `em`.  On return the slot is pinned (host_users) and `stream`
-// is ordered after the slot's last use; the caller launches its kernel and then calls release_ll_slot.
-int32_t acquire_ll_slot(const pmx_model* model, pmx_population* pop, DeviceStream* ds, const pmx_error_model* em,
-                        void* stream, DeviceStream::LLCache** out, bool batch = false) {
-  const int nout = model->d.nout;
-  const auto& hp = pop->hp;
-  std::lock_guard<std::mutex> lock(pop->mu);
-  if (!pop->ll_ready) {  // observation-side inputs, once per population
-    int32_t rc;
-    std::vector<int32_t> oq(hp.obs_outeq.begin(), hp.obs_outeq.end());
-    if ((rc = upload(hp.obs_value, &pop->d_obs_y, &pop->ll_allocs)) != PMX_OK) return rc;
-    if ((rc = upload(oq, &pop->d_obs_outeq, &pop->ll_allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.obs_errorpoly, &pop->d_obs_poly, &pop->ll_allocs)) != PMX_OK) return rc;
-    if ((rc = upload(hp.obs_censor, &pop->d_obs_cens, &pop->ll_allocs)) != PMX_OK) return rc;
-    for (int64_t r = 0; r < hp.n_obs; ++r) {
-      if (std::isnan(hp.obs_value[static_cast<size_t>(r)])) continue;
-      const int q = hp.obs_outeq[static_cast<size_t>(r)];
-      if (q >= 0 && q < 32) pop->valued_outeq_mask |= (1u << q);
-      if (!hp.obs_censor.empty() && hp.obs_censor[static_cast<size_t>(r)] != PMX_CENSOR_NONE) pop->any_censored = true;
-    }
-    pop->ll_ready = true;
-  }
-  for (int q = 0; q < 32; ++q) {
-    if (!((pop->valued_outeq_mask >> q) & 1u)) continue;
-    if (q >= nout) return fail(PMX_ERR_OUTEQ_OUT_OF_RANGE, "observation outeq >= nout");
-    // log_likelihood_matrix: MissingErrorModel fails the call (error_model.rs:1045-1080 through matrix.rs:83,104).
-    // log_likelihood_batch: ResidualErrorModels::total_log_likelihood gives such a SUBJECT -inf and the call succeeds
-    // (residual_error.rs:413-425): the table fill poisons the rows of that output (pmx_ll_prepare_obs), the subject's sum
-    // comes out NaN with PMX_PAIR_NONFINITE, the batch entry points map that to -inf.
-    if (!batch && (em[q].kind < PMX_EM_ADDITIVE || em[q].kind > PMX_EM_RES_EXPONENTIAL))
-      return fail(PMX_ERR_ERROR_MODEL, "MissingErrorModel: output " + std::to_string(q) + " has observations but no error model");
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  DeviceStream::LLCache* slot = nullptr;
-  for (auto& c : ds->ll_cache)
-    if (static_cast<int>(c.em.size()) == nout && std::memcmp(c.em.data(), em, sizeof(pmx_error_model) * nout) == 0) {
-      slot = &c;
-      break;
-    }
-  const bool hit = slot != nullptr;
-  if (!hit) {
-    constexpr size_t kSlots = 4;
-    if (ds->ll_cache.size() >= kSlots)  // least recently used slot nobody is about to launch on
-      for (auto& c : ds->ll_cache)
-        if (c.host_users == 0 && (slot == nullptr || c.stamp < slot->stamp)) slot = &c;
-    if (slot == nullptr) {
-      ds->ll_cache.emplace_back();
-      slot = &ds->ll_cache.back();
-      void* p = nullptr;
-      PMX_HIP(hipMalloc(&p, static_cast<size_t>(hp.n_obs > 0 ? hp.n_obs : 1) * 4 * sizeof(double)));
-      ds->allocs.push_back(p);
-      slot->d_obs = static_cast<double*>(p);
-      if (ds->cobs_size > 0) {
-        // (+ 2 G doubles of slack: the kernel requests a step's observation block before it knows the step has one)
-        PMX_HIP(hipMalloc(&p, static_cast<size_t>(ds->cobs_size + 2 * ds->cls.G) * sizeof(double)));
-        ds->allocs.push_back(p);
-        slot->d_cobs = static_cast<double*>(p);
-      }
-      PMX_HIP(hipMalloc(&p, sizeof(int32_t)));
-      ds->allocs.push_back(p);
-      slot->d_err = static_cast<int32_t*>(p);
-      PMX_HIP(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
-      PMX_HIP(hipEventRecord(slot->ev, st));
-    }
-  }
-  PMX_HIP(hipStreamWaitEvent(st, slot->ev, 0));  // after the slot's last fill / read, whatever stream that was on
-  if (!hit) {
-    pmx::LLPrepareArgs a{};
-    a.obs_y = pop->d_obs_y;
-    a.obs_outeq = pop->d_obs_outeq;
-    a.obs_poly = pop->d_obs_poly;
-    a.obs_cens = pop->d_obs_cens;
-    for (int q = 0; q < PMX_MAX_OUT; ++q) a.em[q] = q < nout ? em[q] : pmx_error_model{};
-    a.n_obs = hp.n_obs;
-    a.obs4 = slot->d_obs;
-    a.err = slot->d_err;
-    a.chunk_row = ds->cls.chunk_row;
-    a.chunk_n = ds->cls.chunk_n;
-    a.chunk_nobs = ds->d_chunk_nobs;
-    a.chunk_obs_off = ds->d_chunk_obs_off;
-    a.chunk_cls = ds->cls.chunk_cls;
-    a.cls_prog_off = ds->cls.cls_prog_off;
-    a.prog_meta = ds->cls.prog_meta;
-    a.n_chunks = ds->cobs_size > 0 ? ds->cls.n_chunks : 0;
-    a.G = ds->cls.G;
-    a.cobs = slot->d_cobs;
-    a.stream = stream;
-    // Filling: until the event below is recorded behind the fill, the slot must not be hit by another host thread (its
-    // stream would only wait for the slot's PREVIOUS use and read a half-written table).  pop->mu is held throughout; a
-    // failed fill leaves the slot keyless.
-    slot->em.clear();
-    hipError_t fe = hipMemsetAsync(slot->d_err, 0, sizeof(int32_t), st);
-    if (fe == hipSuccess) fe = pmx::launch_ll_prepare(a);
-    if (fe == hipSuccess) fe = hipEventRecord(slot->ev, st);
-    if (fe != hipSuccess) return fail(PMX_ERR_HIP, std::string("log-likelihood table fill: ") + hipGetErrorString(fe));
-    slot->em.assign(em, em + nout);
-  }
-  slot->stamp = ++ds->ll_stamp;
-  slot->host_users++;
-  *out = slot;
-  return PMX_OK;
-}
-
-void release_ll_slot(pmx_population* pop, DeviceStream::LLCache* slot, void* stream) {
-  std::lock_guard<std::mutex> lock(pop->mu);
-  (void)hipEventRecord(slot->ev, static_cast<hipStream_t>(stream));
-  slot->host_users--;
-}
-
-struct LLRequest {
-  const pmx_error_model* em = nullptr;
-  double* d_ll = nullptr;
-  int64_t ld = 0;
-  const int32_t** d_sigma_err = nullptr;  // out (host form): the slot's invalid-sigma counter
-};
-
-int32_t enqueue(const pmx_model* model, pmx_population* pop, const double* d_theta, int64_t P, int batch,
-                double* d_pred, int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq = nullptr,
-                int state_override = -1) {
-  const pmx_model_desc& d = model->d;
-  if (d.n_covariates != pop->hp.n_cov)
-    return fail(PMX_ERR_INVALID_ARGUMENT, "model declares " + std::to_string(d.n_covariates) +
-                                              " covariates, population carries " + std::to_string(pop->hp.n_cov));
-  DeviceStream* ds = nullptr;
-  int32_t rc = get_stream(pop, key_for(model), &ds);
-  if (rc != PMX_OK) return rc;
-  // range checks the reference performs inside the event loop
-  if (ds->max_input_used >= d.ndrugs)
-    return fail(PMX_ERR_INPUT_OUT_OF_RANGE, "input " + std::to_string(ds->max_input_used) + " >= ndrugs " +
-                                                std::to_string(d.ndrugs));  // equation/mod.rs:322-327
-  if (pop->hp.max_outeq >= d.nout)
-    return fail(PMX_ERR_OUTEQ_OUT_OF_RANGE,
-                "outeq " + std::to_string(pop->hp.max_outeq) + " >= nout " + std::to_string(d.nout));
-  if (pop->hp.n_subjects == 0) return PMX_OK;
-
-  pmx::LaunchArgs a{};
-  a.m.eq_kind = d.eq_kind;
-  a.m.kernel = d.kernel;
-  a.m.nparams = d.nparams;
-  a.m.n_cov = d.n_covariates;
-  a.m.n_derived = d.n_derived;
-  a.m.n_bind = d.n_bind;
-  a.m.nout = d.nout;
-  a.m.pm = d.pmetrics_indexing ? 1 : 0;
-  a.m.has_init = model->has_init ? 1 : 0;
-  a.m.rk4_h_max = d.rk4_h_max;
-  a.m.ode_rtol = d.ode_rtol;
-  a.m.ode_atol = d.ode_atol;
-  a.adaptive = (d.eq_kind == PMX_EQ_ODE && d.ode_solver != PMX_SOLVER_RK4) ? 1 : 0;
-  a.m.ode_stiff = (d.eq_kind == PMX_EQ_ODE && d.ode_solver == PMX_SOLVER_ROS2) ? 1 : 0;
-  std::memcpy(a.m.derived, d.derived, sizeof(d.derived));
-  std::memcpy(a.m.bind, d.bind, sizeof(d.bind));
-  std::memcpy(a.m.out, d.out, sizeof(d.out));
-  a.m.state_override = state_override;  // (the run-time-compiled walkers read it)
-  if (state_override >= 0)  // Prediction::state: every output equation reads the raw amount of one state
-    for (int o = 0; o < PMX_MAX_OUT; ++o) a.m.out[o] = pmx_out{state_override, PMX_SRC_NONE, 0};
-  for (int o = 0; o < PMX_MAX_OUT; ++o) {
-    a.m.out_vol_theta[o] = -1;
-    if (a.m.out[o].vol_src == PMX_SRC_PRIMARY) a.m.out_vol_theta[o] = a.m.out[o].vol_index;
-    if (a.m.out[o].vol_src == PMX_SRC_DERIVED && a.m.out[o].vol_index >= 0 && a.m.out[o].vol_index < PMX_MAX_DERIVED)
-      a.m.out_vol_theta[o] = d.derived[a.m.out[o].vol_index].src_param;
-  }
-  std::memcpy(a.m.init_param, d.init_param, sizeof(d.init_param));
-  std::memcpy(a.m.bolus_dest, d.bolus_dest, sizeof(d.bolus_dest));
-  std::memcpy(a.m.infusion_dest, d.infusion_dest, sizeof(d.infusion_dest));
-  std::memcpy(a.m.fa_param, d.fa_param, sizeof(d.fa_param));
-  for (int i = 0; i < PMX_MAX_INPUTS; ++i) {
-    if (d.fa_param[i] >= 0) a.m.has_fa = 1;
-    if (d.lag_param[i] >= 0 && a.m.n_lag_slots < pmx::kMaxLagSlots && !model->user_ode) {
-      a.m.lag_input[a.m.n_lag_slots] = i;
-      a.m.lag_param[a.m.n_lag_slots] = d.lag_param[i];
-      a.m.lag_dest[a.m.n_lag_slots] = (d.eq_kind == PMX_EQ_ODE && d.bolus_dest[i] >= 0) ? d.bolus_dest[i] : i;
-      a.m.n_lag_slots++;
-    }
-  }
-  a.ops = ds->dev;
-  {
-    // ODE PAIR kernel, steps per trip of the lane state machine (pmx_ode.hpp ode_pair_body): tools/experiments/steps_per_trip_sweep.sh
-    const int64_t n_pairs = batch ? pop->hp.n_subjects : pop->hp.n_subjects * P;
-    const int32_t spt_tuned = tunables().steps_per_trip;
-    a.ops.steps_per_trip = spt_tuned > 0 ? spt_tuned : (n_pairs <= 131072 ? 48 : 32);
-  }
-  a.theta = d_theta;
-  a.P = batch ? 1 : P;
-  a.S = pop->hp.n_subjects;
-  a.pred = d_pred;
-  a.ld = batch ? 1 : ld;
-  a.status = d_status;
-  a.batch = batch;
-  a.dyn = model->dyn ? 1 : 0;
-  a.stream = stream;
-  a.cls = ds->cls;
-  a.use_classes = ds->cls.n_chunks > 0 ? 1 : 0;
-  {
-    // the lean walker serves the plain models: rate constants and volumes fixed per lane, no lag, no pm_ pad slot
-    bool plain = d.eq_kind == PMX_EQ_ANALYTICAL && !model->dyn && !model->custom && a.m.n_lag_slots == 0 && !d.pmetrics_indexing &&
-                 std::getenv("PMX_DISABLE_STEPS") == nullptr;
-    for (int o = 0; o < d.nout && o < PMX_MAX_OUT; ++o)
-      if (a.m.out[o].vol_src == PMX_SRC_DERIVED && d.derived[a.m.out[o].vol_index].n_factors > 0) plain = false;
-    if (plain) a.steps = ds->steps;
-  }
-  // the stream's codes were written for key.prop_cache_slots slots; the kernel decodes them with the same number
-  a.prop_slots = ds->prop_cache_used > 0 ? ds->key.prop_cache_slots : 0;
-  a.no_rates = (ds->no_rates && d.eq_kind == PMX_EQ_ANALYTICAL && ds->dev.op_kfac != nullptr && std::getenv("PMX_DISABLE_DYN3") == nullptr) ? 1 : 0;
-  a.eig_reuse = ds->eig_reuse ? 1 : 0;
-  a.dyn_tile = tunables().dyn_tile;  // (0 = the default tile; 64 and 256 measured the same with one slot)
-  DeviceStream::LLCache* slot = nullptr;
-  struct SlotGuard {  // the slot is released (event recorded on the stream) however this function leaves
-    pmx_population* pop;
-    DeviceStream::LLCache** slot;
-    void* stream;
-    ~SlotGuard() {
-      if (*slot) release_ll_slot(pop, *slot, stream);
-    }
-  } slot_guard{pop, &slot, stream};
-  if (llreq != nullptr) {
-    rc = acquire_ll_slot(model, pop, ds, llreq->em, stream, &slot, batch != 0);
-    if (rc != PMX_OK) return rc;
-    a.ops.ll_obs = slot->d_obs;
-    a.ops.ll_out = llreq->d_ll;
-    a.ops.ll_ld = llreq->ld;
-    a.cls.cobs = slot->d_cobs;
-    a.cls.chunk_obs_off = ds->d_chunk_obs_off;
-    if (llreq->d_sigma_err) *llreq->d_sigma_err = slot->d_err;
-    a.ll_censored = pop->any_censored ? 1 : 0;  // (known once the population's observation arrays are on the device)
-    for (int q = 0; q < d.nout && q < PMX_MAX_OUT; ++q)
-      if (llreq->em[q].kind >= PMX_EM_RES_CONSTANT) a.ll_censored = 1;  // residual models fold from the full records too
-  }
-  // GRID (lane = support point, wave-uniform op stream) vs PAIR (lane = pair, divergent streams): measured crossovers
-  // (tools/experiments/pairgrid_sweep.sh) are 8 support points when the classed kernel serves most subjects, ~48 when every
-  // subject goes through the generic walker (a GRID wave with few live lanes still pays the whole walk); ODE: 32.
-  int64_t grid_min_p = 32;
-  if (d.eq_kind == PMX_EQ_ANALYTICAL)
-    grid_min_p = (a.use_classes && 2 * ds->n_classed_subjects >= a.S) ? 8 : 48;
-  if (const int32_t g = tunables().grid_min_p; g > 0) grid_min_p = g;  // tuning experiments
-  a.tune_cpb = tunables().cpb;
-  a.tune_ll_old = tunables().ll_old ? 1 : 0;
-  if (!batch && P >= grid_min_p) {
-    a.mode = pmx::MODE_GRID;
-    a.n_ptiles = static_cast<int32_t>((P + 255) / 256);
-    // enough blocks to fill 256 CUs several times over, few enough that the per-block
-    // rate-constant setup stays amortised
-    int64_t chunk = (a.S * a.n_ptiles) / 8192;
-    if (chunk < 1) chunk = 1;
-    if (chunk > 64) chunk = 64;
-    a.s_chunk = static_cast<int32_t>(chunk);
-  } else {
-    a.mode = pmx::MODE_PAIR;
-    a.n_ptiles = 1;
-    a.s_chunk = 1;
-  }
-  const int64_t blocks = a.mode == pmx::MODE_GRID ? ((a.S + a.s_chunk - 1) / a.s_chunk) * a.n_ptiles
-                                                  : ((batch ? a.S : a.S * a.P) + 255) / 256;
-  if (blocks > 0x7fffffffLL) return fail(PMX_ERR_INVALID_ARGUMENT, "grid too large for one launch");
-  // Status bytes need no memset before the launch (it cost ~70 us of serialisation per pass): the PAIR and ODE kernels
-  // write every pair's byte; the analytical GRID kernels clear a subject's bytes with 8-byte stores when the row
-  // length allows (mode 1) and otherwise write every byte too (mode 2).  Every subject is visited: the generic walker
-  // owns the subjects no class holds, empty ones included.
-  a.cls.zero_status = 0;
-  if (d_status != nullptr && a.mode == pmx::MODE_GRID && d.eq_kind == PMX_EQ_ANALYTICAL)
-    a.cls.zero_status = (P % 8 == 0 && reinterpret_cast<uintptr_t>(d_status) % 8 == 0 && (ds->cls.n_chunks == 0 || ds->cls.G <= 8)) ? 1 : 2;
-  const char* name = "";
-  hipError_t e;
-  if (model->custom) {
-    // hiprtc-compiled model: resolve (once per device) and launch the matching entry point of its module
-    const pmx::JitModule* jm = nullptr;
-    {
-      std::lock_guard<std::mutex> lock(model->jit_mu);
-      // closure walkers keep 64 landing times per lane; an occasion with more takes the build with the scan path in
-      const bool big = (d.eq_kind == PMX_EQ_ANALYTICAL || model->user_ode) && ds->max_lagb_per_list > pmx::kUserLagKept;
-      if (big && model->jit_code_big.empty()) {
-        pmx::JitSpec sp = model->jit_spec;
-        sp.big_lists = true;
-        std::string log;
-        if (!pmx::jit_compile(sp, &model->jit_code_big, &log))
-          return fail(PMX_ERR_HIP, "hiprtc could not compile the big-lists build of the model:\n" + log);
-      }
-      auto& modules = big ? model->jit_modules_big : model->jit_modules;
-      auto it = modules.find(pop->device);
-      if (it == modules.end()) {
-        pmx::JitModule mod;
-        const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod,
-                                            d.eq_kind == PMX_EQ_ANALYTICAL ? pmx::JIT_ANALYTICAL
-                                                                           : (model->user_ode ? pmx::JIT_ODE_USER : pmx::JIT_ODE));
-        if (le != hipSuccess) return fail(PMX_ERR_HIP, std::string("loading the compiled model: ") + hipGetErrorString(le));
-        it = modules.emplace(pop->device, mod).first;
-      }
-      jm = &it->second;
-    }
-    const bool ua = d.eq_kind == PMX_EQ_ANALYTICAL;  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][ADAPT]
-    const int lag = (!ua && !model->user_ode && a.m.n_lag_slots > 0) ? 1 : 0, ll = a.ops.ll_obs != nullptr ? 1 : 0,
-              ad = (!ua && a.adaptive) ? 1 : 0;
-    const int mode = a.mode == pmx::MODE_GRID ? 0 : 1;
-    static const char* const kNames[3][2][2] = {
-        {{"pmx_jit_ode_rk4_grid", "pmx_jit_ode_rk4_grid<lag>"}, {"pmx_jit_ode_rk4_pair", "pmx_jit_ode_rk4_pair<lag>"}},
-        {{"pmx_jit_ode_dopri5_grid", "pmx_jit_ode_dopri5_grid<lag>"}, {"pmx_jit_ode_dopri5_pair", "pmx_jit_ode_dopri5_pair<lag>"}},
-        {{"pmx_jit_ode_ros2_grid", "pmx_jit_ode_ros2_grid<lag>"}, {"pmx_jit_ode_ros2_pair", "pmx_jit_ode_ros2_pair<lag>"}}};
-    const int sv = ad ? (a.m.ode_stiff ? 2 : 1) : 0;  // (the same compiled entry point serves both adaptive steppers)
-    name = kNames[sv][mode][lag];
-    if (ua) name = mode == 0 ? "pmx_jit_analytical_grid" : "pmx_jit_analytical_pair";
-    static const char* const kUser[3][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
-                                            {"pmx_jit_ode_user_dopri5_grid", "pmx_jit_ode_user_dopri5_pair"},
-                                            {"pmx_jit_ode_user_ros2_grid", "pmx_jit_ode_user_ros2_pair"}};
-    if (model->user_ode) name = kUser[sv][mode];
-    // (experiment hook, tools/experiments/user_static: PMX_DEBUG_STATIC_SO names a shared object holding the SAME translation
-    // unit compiled ahead of time by hipcc, with a launcher for its GRID prediction entry point)
-    typedef int (*static_launch_t)(const void*, const void*, const double*, int64_t, int64_t, int32_t, int32_t, double*, int64_t,
-                                   uint8_t*, uint32_t, uint32_t, void*);
-    static static_launch_t s_static = []() -> static_launch_t {
-      const char* so = std::getenv("PMX_DEBUG_STATIC_SO");
-      if (!so) return nullptr;
-      void* h = dlopen(so, RTLD_NOW | RTLD_LOCAL);
-      return h ? reinterpret_cast<static_launch_t>(dlsym(h, "pmx_static_launch")) : nullptr;
-    }();
-    if (s_static && mode == 0 && !ll && a.S > 0 && a.P > 0) {
-      const int64_t n_chunks = (a.S + a.s_chunk - 1) / a.s_chunk;
-      const int rc_s = s_static(&a.m, &a.ops, a.theta, a.P, a.S, a.s_chunk, a.n_ptiles, a.pred, a.ld, a.status,
-                                static_cast<uint32_t>(n_chunks * a.n_ptiles), a.P <= 64 ? 64u : (a.P <= 128 ? 128u : 256u), stream);
-      e = rc_s == 0 ? hipSuccess : hipErrorUnknown;
-      name = "pmx_static_agrid";
-    } else if (a.S <= 0 || (a.P <= 0 && !a.batch)) {
-      e = hipSuccess;
-    } else if (mode == 0) {
-      const int64_t n_chunks = (a.S + a.s_chunk - 1) / a.s_chunk;
-      void* args[] = {&a.m, &a.ops, &a.theta, &a.P, &a.S, &a.s_chunk, &a.n_ptiles, &a.pred, &a.ld, &a.status};
-      e = hipModuleLaunchKernel(jm->fn[0][lag][ll][ad], static_cast<uint32_t>(n_chunks * a.n_ptiles), 1, 1,
-                                a.P <= 64 ? 64u : (a.P <= 128 ? 128u : 256u), 1, 1, 0,
-                                static_cast<hipStream_t>(stream), args, nullptr);
-    } else {
-      const int64_t n_pairs = a.batch ? a.S : a.S * a.P;
-      void* args[] = {&a.m, &a.ops, &a.theta, &a.P, &a.S, &a.batch, &a.pred, &a.ld, &a.status};
-      e = hipModuleLaunchKernel(jm->fn[1][lag][ll][ad], static_cast<uint32_t>((n_pairs + 255) / 256), 1, 1, 256, 1, 1, 0,
-                                static_cast<hipStream_t>(stream), args, nullptr);
-    }
-  } else {
-    e = pmx::launch_predict(a, &name);
-  }
-  g_kernel_name = name;
-  if (e != hipSuccess) return fail(PMX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return PMX_OK;
-}
 
 // ---- host-pointer forms -------------------------------------------------------------------------------------------
 int32_t ws_get(pmx_population* pop, HostWorkspace** out) {
@@ -1708,8 +883,24 @@ int32_t pmx_predict_batch_device(const pmx_model* model, const pmx_population* c
 namespace {
 struct DebugOwner {
   pmx::HostPopulation hp;
-  pmx::OpStream os;
+  pmx::StreamPlan sp;
 };
+
+// the stream plan of a (population, model) pair exactly as a launch would build it: same key, same class-plan switches
+int32_t debug_plan(const pmx_population_desc* pop, const pmx_model_desc* model, pmx::HostPopulation* hp, pmx::StreamPlan* sp,
+                   pmx::CompileKey* key) {
+  pmx_model* m = nullptr;
+  int32_t rc = pmx_model_create(model, &m);
+  if (rc != PMX_OK) return rc;
+  std::unique_ptr<pmx_model> mg(m);
+  std::string err;
+  rc = pmx::build_host_population(pop, hp, &err);
+  if (rc != PMX_OK) return fail(rc, err);
+  const pmx::Tunables tun = pmx::tunables();
+  *key = key_for(m, tun, hp->has_infusions);
+  rc = pmx::plan_stream(*hp, *key, tun.cls, sp, &err);
+  return rc != PMX_OK ? fail(rc, err) : PMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1718,17 +909,11 @@ int32_t pmx_debug_compile(const pmx_population_desc* pop, const pmx_model_desc* 
   g_err.clear();
   if (!pop || !model || !out) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
   std::memset(out, 0, sizeof(*out));
-  pmx_model* m = nullptr;
-  int32_t rc = pmx_model_create(model, &m);
-  if (rc != PMX_OK) return rc;
-  std::unique_ptr<pmx_model> mg(m);
   auto own = std::make_unique<DebugOwner>();
-  std::string err;
-  rc = pmx::build_host_population(pop, &own->hp, &err);
-  if (rc != PMX_OK) return fail(rc, err);
-  rc = pmx::compile_ops(own->hp, key_for(m), &own->os, &err);
-  if (rc != PMX_OK) return fail(rc, err);
-  const pmx::OpStream& os = own->os;
+  pmx::CompileKey key;
+  const int32_t rc = debug_plan(pop, model, &own->hp, &own->sp, &key);
+  if (rc != PMX_OK) return rc;
+  const pmx::OpStream& os = own->sp.os;
   out->n_subjects = own->hp.n_subjects;
   out->n_ops = os.n_ops;
   out->n_cov = own->hp.n_cov;
@@ -1750,23 +935,15 @@ int32_t pmx_debug_compile(const pmx_population_desc* pop, const pmx_model_desc* 
 int32_t pmx_debug_class_plan(const pmx_population_desc* pop, const pmx_model_desc* model, int64_t* counts) {
   g_err.clear();
   if (!pop || !model || !counts) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
-  pmx_model* m = nullptr;
-  int32_t rc = pmx_model_create(model, &m);
-  if (rc != PMX_OK) return rc;
-  std::unique_ptr<pmx_model> mg(m);
   pmx::HostPopulation hp;
-  pmx::OpStream os;
-  std::string err;
-  rc = pmx::build_host_population(pop, &hp, &err);
-  if (rc != PMX_OK) return fail(rc, err);
-  const pmx::CompileKey key = key_for(m);
-  rc = pmx::compile_ops(hp, key, &os, &err);
-  if (rc != PMX_OK) return fail(rc, err);
+  pmx::StreamPlan sp;
+  pmx::CompileKey key;
+  const int32_t rc = debug_plan(pop, model, &hp, &sp, &key);
+  if (rc != PMX_OK) return rc;
   for (int i = 0; i < 5; ++i) counts[i] = 0;
   counts[3] = hp.n_subjects;
   if (key.class_g > 0) {
-    pmx::ClassPlan cp;
-    pmx::build_class_plan(hp, os, key.class_g, key.class_g / 2, &cp, key.ladder, true, true);
+    const pmx::ClassPlan& cp = sp.cp;
     counts[0] = cp.n_chunks_exact;
     counts[1] = cp.n_chunks - cp.n_chunks_exact;
     counts[2] = cp.n_classed_subjects;

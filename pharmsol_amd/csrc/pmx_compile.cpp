@@ -113,6 +113,7 @@ int32_t build_host_population(const pmx_population_desc* d, HostPopulation* hp, 
       ev_src[dst] = src;
       if (k == PMX_EV_OBSERVATION)
         hp->max_outeq = std::max<int32_t>(hp->max_outeq, d->ev_io[src]);
+      hp->has_infusions |= (k == PMX_EV_INFUSION);
     }
   }
   // prediction rows (event order == flat_predictions order, subject.rs:145-148)
@@ -901,6 +902,136 @@ void build_class_plan(const HostPopulation& hp, const OpStream& os, int32_t G, i
   cp->n_chunks = static_cast<int64_t>(cp->chunk_cls.size());
   cp->chunk_val_off.push_back(static_cast<int64_t>(cp->val.size()));  // sentinel: chunk c's block is [off[c], off[c+1])
   std::sort(cp->generic_subjects.begin(), cp->generic_subjects.end());
+}
+
+namespace {
+
+// packed per-op records (pmx_devtypes.hpp DevOps::op_rec)
+void pack_op_rec(const OpStream& os, const CompileKey& key, std::vector<double>* out) {
+  const bool times = !os.op_t0.empty();
+  if (key.eq_kind == PMX_EQ_ODE) {
+    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 6, 0.0);
+    for (int64_t o = 0; o < os.n_ops; ++o) {
+      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]) | (static_cast<uint64_t>(static_cast<uint32_t>(os.op_n[o])) << 32);
+      std::memcpy(&rec[6 * o], &w, 8);
+      rec[6 * o + 1] = os.op_a[o];
+      rec[6 * o + 2] = os.op_b[o];
+      rec[6 * o + 3] = key.n_rate > 0 ? os.op_rate[o * key.n_rate] : 0.0;
+      rec[6 * o + 4] = times ? os.op_t0[o] : 0.0;
+      rec[6 * o + 5] = times ? os.op_t1[o] : 0.0;
+    }
+    out->swap(rec);
+  } else {  // analytical: {meta (bits), a, b, t0} = 32 bytes
+    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 4, 0.0);
+    for (int64_t o = 0; o < os.n_ops; ++o) {
+      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]);
+      std::memcpy(&rec[4 * o], &w, 8);
+      rec[4 * o + 1] = os.op_a[o];
+      rec[4 * o + 2] = os.op_b[o];
+      rec[4 * o + 3] = times ? os.op_t0[o] : 0.0;
+    }
+    out->swap(rec);
+  }
+}
+
+// one 64-byte record per op for the matrix-free walker (DevOps::op_kfac)
+void pack_op_kfac(const OpStream& os, const CompileKey& key, std::vector<double>* out) {
+  const size_t n_ops = os.op_meta.size();
+  const size_t fw = static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS;
+  std::vector<double> kf(n_ops * 8, 1.0);
+  for (size_t o = 0; o < n_ops; ++o) {
+    for (int j = 0; j < key.kfac_n && j < 7; ++j) {
+      const int dd = key.kfac_map[j];
+      if (dd < 0 || dd >= key.n_derived) continue;
+      double f = 1.0;  // the parameter's factors multiplied out: theta * (f0 * f1) for the descriptor's (theta * f0) * f1
+      for (int q = 0; q < key.derived[dd].n_factors && q < PMX_MAX_FACTORS; ++q) f *= os.op_fac[o * fw + static_cast<size_t>(dd) * PMX_MAX_FACTORS + q];
+      kf[o * 8 + j] = f;
+    }
+    kf[o * 8 + 7] = os.op_a[o];
+  }
+  out->swap(kf);
+}
+
+// what the log-likelihood kernels read of a class plan besides the plan itself: prog_rec, the per-chunk observation
+// counts and block offsets, and the 64-byte chunk headers
+void pack_class_ll(StreamPlan* sp) {
+  const ClassPlan& cp = sp->cp;
+  std::vector<double> prec((cp.prog_meta.size() + 1) * 2, 0.0);
+  for (size_t i = 0; i < cp.prog_meta.size(); ++i) {
+    const uint64_t w = cp.prog_meta[i];
+    std::memcpy(&prec[2 * i], &w, 8);
+    prec[2 * i + 1] = cp.prog_dt[i];
+  }
+  sp->prog_rec.swap(prec);
+  sp->chunk_nobs.resize(static_cast<size_t>(cp.n_chunks));
+  for (int64_t c = 0; c < cp.n_chunks; ++c) {
+    const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
+    int32_t nobs = 0;
+    for (int64_t o = cp.cls_prog_off[cl]; o < cp.cls_prog_off[cl + 1]; ++o) nobs += (cp.prog_meta[static_cast<size_t>(o)] >> 24) & 1u;
+    sp->chunk_nobs[static_cast<size_t>(c)] = nobs;
+  }
+  std::vector<int64_t>& off = sp->chunk_obs_off;
+  off.resize(static_cast<size_t>(cp.n_chunks) + 1);
+  int64_t at = 0;
+  for (int64_t c = 0; c < cp.n_chunks; ++c) {
+    off[static_cast<size_t>(c)] = at;
+    at += (static_cast<int64_t>(sp->chunk_nobs[static_cast<size_t>(c)]) * 2 + 2) * cp.G;
+  }
+  off[static_cast<size_t>(cp.n_chunks)] = at;  // sentinel
+  sp->cobs_size = at;
+  // one 64-byte record per chunk for pmx_analytical_classed_ll (pmx_kernels.hpp DevClassPlan::chunk_hdr): everything
+  // the kernel needs of a chunk in ONE scalar fetch.  32-bit offsets and 16-bit counts: a plan outside those
+  // limits simply keeps the round-2 kernel (chunk_hdr stays empty).
+  bool fits = cp.G <= 8 && at < (int64_t{1} << 32) && static_cast<int64_t>(cp.val.size()) < (int64_t{1} << 32) &&
+              static_cast<int64_t>(cp.prog_meta.size()) < (int64_t{1} << 32);
+  for (size_t cl = 0; cl + 1 < cp.cls_prog_off.size() && fits; ++cl)
+    fits = cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl] < 65536;
+  if (!fits) return;
+  std::vector<uint32_t> hdr((static_cast<size_t>(cp.n_chunks) + 1) * 16, 0);
+  for (int64_t c = 0; c < cp.n_chunks; ++c) {
+    uint32_t* q = &hdr[static_cast<size_t>(c) * 16];
+    const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
+    q[0] = static_cast<uint32_t>(cp.chunk_n[static_cast<size_t>(c)]) |
+           (static_cast<uint32_t>(cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl]) << 16);
+    q[1] = static_cast<uint32_t>(cp.cls_prog_off[cl]);
+    q[2] = static_cast<uint32_t>(cp.chunk_val_off[static_cast<size_t>(c)]);
+    q[3] = static_cast<uint32_t>(off[static_cast<size_t>(c)]);
+    const uint64_t rm = cp.chunk_rate_mask[static_cast<size_t>(c)], fm = cp.cls_fast_mask[cl];
+    q[4] = static_cast<uint32_t>(rm);
+    q[5] = static_cast<uint32_t>(rm >> 32);
+    q[6] = static_cast<uint32_t>(fm);
+    q[7] = static_cast<uint32_t>(fm >> 32);
+    for (int32_t j = 0; j < cp.G; ++j) q[8 + j] = static_cast<uint32_t>(cp.chunk_subj[static_cast<size_t>(c) * cp.G + j]);
+  }
+  sp->chunk_hdr.swap(hdr);
+}
+
+}  // namespace
+
+int32_t plan_stream(const HostPopulation& hp, const CompileKey& key, const ClassTunables& ct, StreamPlan* sp, std::string* err) {
+  OpStream& os = sp->os;
+  const int32_t rc = compile_ops(hp, key, &os, err);
+  if (rc != PMX_OK) return rc;
+  pack_op_rec(os, key, &sp->op_rec);
+  if (key.kfac_n > 0 && !os.op_fac.empty()) pack_op_kfac(os, key, &sp->op_kfac);
+  sp->no_rates = true;  // (analytical streams: a PROP's op_b is its rate)
+  for (size_t o = 0; o < os.op_meta.size() && sp->no_rates; ++o)
+    if ((os.op_meta[o] & 0xffu) == OP_PROP && os.op_b[o] != 0.0) sp->no_rates = false;
+  sp->eig_reuse = false;  // (covariate streams: bit 27 of a PROP = "same rate constants as the previous built segment")
+  if (key.prop_cache_slots > 0 && !os.op_fac.empty())
+    for (size_t o = 0; o < os.op_meta.size() && !sp->eig_reuse; ++o)
+      if ((os.op_meta[o] & 0xffu) == OP_PROP && (os.op_meta[o] & (1u << 27))) sp->eig_reuse = true;
+  sp->prop_reuse_fraction = os.n_prop > 0 ? static_cast<double>(os.n_prop_reused) / static_cast<double>(os.n_prop) : 0.0;
+  if (key.eq_kind == PMX_EQ_ANALYTICAL && !key.user_cov && key.lag_mask == 0 && os.op_fac.empty())
+    build_step_stream(os, &sp->subj_step_off, &sp->step_rec);
+  if (key.class_g > 0) {
+    const int32_t min_class = ct.min_class > 0 ? ct.min_class : key.class_g / 2;
+    const bool spread = ct.spread < 0 ? true : ct.spread != 0;  // (0.94-0.97 vs 1.05-1.11 ms on C3 in most allocations, never slower: tools/experiments/alloc_tune.py)
+    const bool loose = ct.loose < 0 ? true : ct.loose != 0;  // subjects without a shared design still share a program shape: batched with per-member step lengths
+    build_class_plan(hp, os, key.class_g, min_class, &sp->cp, key.ladder, spread, loose);
+    if (sp->cp.n_chunks > 0) pack_class_ll(sp);
+  }
+  return PMX_OK;
 }
 
 }  // namespace pmx

@@ -39,6 +39,7 @@ struct HostPopulation {
   std::vector<double> ev_time, ev_value, ev_dur;
   std::vector<uint8_t> ev_kind;
   std::vector<uint16_t> ev_io;
+  bool has_infusions = false;  // some event is an infusion (a shard holds the flag of its own events)
   std::vector<int64_t> subj_obs_off;  // [S+1]
   // observation bookkeeping in prediction order
   std::vector<double> obs_time;
@@ -193,5 +194,34 @@ int32_t build_host_population(const pmx_population_desc* d, HostPopulation* out,
 
 // Flatten into an op stream for one model flavour.
 int32_t compile_ops(const HostPopulation& hp, const CompileKey& key, OpStream* out, std::string* err);
+
+// How the class plan of a stream is built (the PMX_TUNE_MIN_CLASS / _SPREAD / _LOOSE switches; defaults = the library's).
+struct ClassTunables {
+  int32_t min_class = 0;           // smallest class that is batched; 0 = class_g / 2
+  int32_t spread = -1, loose = -1; // -1 = library default (both on)
+};
+
+// Everything a (population, model flavour) pair puts on the device, as host arrays: the op stream, the record layouts
+// the kernels decode bit for bit, and what a launch needs to know about the stream.  Pure host code: plan_stream is
+// what the launch path uploads and what the debug views (pmx_debug_compile, pmx_debug_class_plan) show.
+struct StreamPlan {
+  OpStream os;
+  std::vector<double> op_rec;   // DevOps::op_rec: ODE [n_ops][6] = {meta | n << 32 (bits), a, b, rate[0], t0, t1};
+                                //   analytical [n_ops][4] = {meta (bits), a, b, t0}
+  std::vector<double> op_kfac;  // DevOps::op_kfac, [n_ops][8] (key.kfac_n > 0 and the stream carries factors)
+  std::vector<int64_t> subj_step_off;  // DevSteps (analytical streams without lag, closures or covariate factors)
+  std::vector<double> step_rec;
+  ClassPlan cp;                         // key.class_g > 0; n_chunks == 0: nothing classed
+  std::vector<double> prog_rec;         // DevClassPlan::prog_rec, [n_prog_steps + 1][2] = {meta (bits), dt}; last = padding
+  std::vector<int32_t> chunk_nobs;      // [n_chunks] observations per member of the chunk's class
+  std::vector<int64_t> chunk_obs_off;   // [n_chunks + 1] where each chunk's block {[G] constant sums, [G] flags,
+                                        //   [observation][value|weight][G]} starts in a log-likelihood slot's cobs
+  int64_t cobs_size = 0;
+  std::vector<uint32_t> chunk_hdr;      // DevClassPlan::chunk_hdr, [n_chunks + 1][16]; empty: the plan does not fit
+  bool no_rates = false;                // no PROP of the stream has an active infusion
+  bool eig_reuse = false;               // some PROP repeats the previous built segment's covariate factor row (bit 27)
+  double prop_reuse_fraction = 0.0;     // share of PROP ops that take a kept propagator
+};
+int32_t plan_stream(const HostPopulation& hp, const CompileKey& key, const ClassTunables& ct, StreamPlan* out, std::string* err);
 
 }  // namespace pmx

@@ -1874,193 +1874,108 @@ __global__ __launch_bounds__(kBlock) void pmx_ode_rk4_pair(DevModel m, DevOps op
 // ------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------
-// GRID launches: a support grid smaller than one 256-lane tile runs with just the waves it needs (whole waves of
-// lanes beyond n_support would otherwise walk every subject for nothing: P = 64 wasted 3 of 4 waves).
-inline uint32_t grid_threads(int64_t P) {
-  return P <= 64 ? 64u : (P <= 128 ? 128u : static_cast<uint32_t>(kBlock));  // (192-thread blocks measured slower than 256)
+// Policy-free: which kernel, which variant and which geometry is the route's (pmx_launch.cpp plan_routes).
+template <int KID, bool DYN, bool LAG, bool LL, bool PERDT, bool CENS>
+void launch_classed(const LaunchArgs& a, const Route& r) {
+  hipLaunchKernelGGL((pmx_analytical_classed<KID, LL, PERDT, LAG, CENS, (DYN && PERDT)>), dim3(static_cast<uint32_t>(r.blocks)),
+                     dim3(r.threads), 0, static_cast<hipStream_t>(a.stream), a.m, a.ops, a.cls, a.theta, a.P, r.cpb, r.n_ptiles,
+                     a.pred, a.ld, a.status);
 }
 
 template <int KID, bool DYN, bool LAG>
-hipError_t launch_analytical(const LaunchArgs& a, const char** name) {
-  static const char* const kNameGrid = DYN ? "pmx_analytical_grid<dyn>" : (LAG ? "pmx_analytical_grid<lag>" : "pmx_analytical_grid");
-  static const char* const kNamePair = DYN ? "pmx_analytical_pair<dyn>" : (LAG ? "pmx_analytical_pair<lag>" : "pmx_analytical_pair");
+hipError_t launch_analytical(const LaunchArgs& a, const Route& r) {
   hipStream_t st = static_cast<hipStream_t>(a.stream);
-  if (a.mode == MODE_GRID) {
-    int64_t n_walk = a.S;
-    const int32_t* list = nullptr;
-    *name = kNameGrid;
-    if constexpr (!(DYN && LAG)) {
-      if (a.use_classes && a.cls.n_chunks > 0) {
-        *name = "pmx_analytical_classed";
-        // enough blocks to fill the chip several times over, few enough that lane_setup stays amortised
-        // (chunks are taken in grid-stride order; one chunk per block up to 32k blocks measured best: tools/experiments/cpb_on_one_allocation.py)
-        // (the log-likelihood variant writes almost nothing: it prefers fewer, longer blocks that amortise the lane setup)
-        const bool ll = a.ops.ll_obs != nullptr;
-        const int64_t n_exact = a.cls.n_chunks_exact, n_loose = a.cls.n_chunks - a.cls.n_chunks_exact;
-        // (the loose launch is FP64-bound too and behaves the same: 4 chunks per block 1.83 ms, one 1.88 ms, eight 1.84 ms
-        // on jittered C3, profiles/r02/loose_chunks_per_block.txt)
-        auto blocks_for = [&](int64_t n, bool loose, int64_t* cpb_out) {
-          int64_t cpb = (n * a.n_ptiles) / ((ll || loose) ? 8192 : 32768);
-          if (cpb < 1) cpb = 1;
-          if (cpb > (loose && !ll ? 4 : 8)) cpb = loose && !ll ? 4 : 8;
-          if (a.tune_cpb > 0) cpb = a.tune_cpb;  // tuning experiments (PMX_TUNE_CPB, read once by pmx_api.cpp)
-          *cpb_out = cpb;
-          return ((n + cpb - 1) / cpb + 7) / 8 * 8;  // whole XCD groups
-        };
-        auto launch_cls = [&](auto ll_c, auto perdt_c, auto cens_c, int64_t n) {
-          int64_t cpb = 1;
-          const int64_t cblocks = blocks_for(n, decltype(perdt_c)::value, &cpb);
-          hipLaunchKernelGGL((pmx_analytical_classed<KID, decltype(ll_c)::value, decltype(perdt_c)::value, LAG, decltype(cens_c)::value,
-                                                     (DYN && decltype(perdt_c)::value)>),
-                             dim3(static_cast<uint32_t>(cblocks * a.n_ptiles)), dim3(grid_threads(a.P)), 0, st, a.m, a.ops, a.cls,
-                             a.theta, a.P, static_cast<int32_t>(cpb), a.n_ptiles, a.pred, a.ld, a.status);
-        };
-        using T = std::true_type;
-        using F = std::false_type;
-        const bool cens = ll && a.ll_censored != 0;
-        if (n_exact > 0) {
-          if (LAG) *name = ll ? "pmx_analytical_classed<ll,lag>" : "pmx_analytical_classed<lag>";
-          else if (ll) *name = "pmx_analytical_classed<ll>";
-          bool done = false;
-          if constexpr (!LAG && !DYN) {
-            if (ll && a.cls.prog_rec != nullptr && a.cls.chunk_hdr != nullptr && a.tune_ll_old == 0 &&
-                a.ops.ll_ld < (int64_t{1} << 28)) {  // exact classes of a plain model: the pipelined kernel
-              int64_t cpb = 1;
-              const int64_t cblocks = blocks_for(n_exact, false, &cpb);
-              if (cens)
-                hipLaunchKernelGGL((pmx_analytical_classed_ll<KID, true>), dim3(static_cast<uint32_t>(cblocks * a.n_ptiles)),
-                                   dim3(grid_threads(a.P)), 0, st, a.m, a.ops, a.cls, a.theta, a.P, a.n_ptiles, a.status);
-              else
-                hipLaunchKernelGGL((pmx_analytical_classed_ll<KID, false>), dim3(static_cast<uint32_t>(cblocks * a.n_ptiles)),
-                                   dim3(grid_threads(a.P)), 0, st, a.m, a.ops, a.cls, a.theta, a.P, a.n_ptiles, a.status);
-              *name = "pmx_analytical_classed_ll";
-              done = true;
-            }
-          }
-          if (done) {
-          } else if (!ll) launch_cls(F{}, F{}, F{}, n_exact);
-          else if (cens) launch_cls(T{}, F{}, T{}, n_exact);
-          else launch_cls(T{}, F{}, F{}, n_exact);
-        }
-        if constexpr (!LAG) {
-          if (n_loose > 0) {  // subjects that share a program shape but not its step lengths
-            if (n_exact == 0) *name = ll ? "pmx_analytical_classed<ll,loose>" : "pmx_analytical_classed<loose>";
-            if (DYN) *name = ll ? "pmx_analytical_classed<ll,dyn>" : "pmx_analytical_classed<dyn>";
-            if (!ll) launch_cls(F{}, T{}, F{}, n_loose);
-            else if (cens) launch_cls(T{}, T{}, T{}, n_loose);
-            else launch_cls(T{}, T{}, F{}, n_loose);
-          }
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        n_walk = a.cls.n_generic;
-        list = a.cls.generic_subjects;
-        if (n_walk == 0) return hipSuccess;
+  const dim3 grid(static_cast<uint32_t>(r.blocks)), block(r.threads);
+  const int32_t* list = r.leftover ? a.cls.generic_subjects : nullptr;
+  switch (r.family) {
+    case R_CLASSED_LL:
+      if constexpr (!LAG && !DYN) {
+        if (r.cens) hipLaunchKernelGGL((pmx_analytical_classed_ll<KID, true>), grid, block, 0, st, a.m, a.ops, a.cls, a.theta, a.P, r.n_ptiles, a.status);
+        else hipLaunchKernelGGL((pmx_analytical_classed_ll<KID, false>), grid, block, 0, st, a.m, a.ops, a.cls, a.theta, a.P, r.n_ptiles, a.status);
       }
-    }
-    int32_t s_chunk = a.s_chunk;
-    if (list != nullptr) {
-      int64_t ch = (n_walk * a.n_ptiles) / 8192;
-      s_chunk = static_cast<int32_t>(ch < 1 ? 1 : (ch > 64 ? 64 : ch));
-    }
-    // tile = support points per block.  With kept propagators (DYN) the LDS cache is sized per lane, so the tile also
-    // sets the occupancy: a.dyn_tile (64 / 128 / 256, pmx_api.cpp) was picked for that.
-    uint32_t threads = grid_threads(a.P);
-    int32_t n_ptiles = a.n_ptiles;
-    size_t lds = 0;
-    if (DYN && a.prop_slots > 0) {
-      if (a.dyn_tile > 0 && static_cast<uint32_t>(a.dyn_tile) < threads) threads = static_cast<uint32_t>(a.dyn_tile);
-      n_ptiles = static_cast<int32_t>((a.P + threads - 1) / threads);
-      lds = static_cast<size_t>(a.prop_slots) * sizeof(typename LaneModel<KID>::S::Prop) * threads;
-    }
-    const int64_t n_chunks = (n_walk + s_chunk - 1) / s_chunk;
-    const int64_t blocks = n_chunks * n_ptiles;
-    if constexpr (!DYN && !LAG) {
-      if (a.steps.step_rec != nullptr) {  // plain model: the lean walker over fused step records
-        *name = (list != nullptr) ? *name : "pmx_analytical_steps";
-        if (a.ops.ll_obs != nullptr)
-          hipLaunchKernelGGL((pmx_analytical_steps<KID, true>), dim3(static_cast<uint32_t>(blocks)), dim3(threads), 0, st, a.m, a.ops,
-                             a.steps, a.theta, a.P, n_walk, s_chunk, n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status);
+      break;
+    case R_CLASSED:
+      if (!r.loose) {
+        if (!r.ll) launch_classed<KID, DYN, LAG, false, false, false>(a, r);
+        else if (r.cens) launch_classed<KID, DYN, LAG, true, false, true>(a, r);
+        else launch_classed<KID, DYN, LAG, true, false, false>(a, r);
+      } else if constexpr (!LAG) {
+        if (!r.ll) launch_classed<KID, DYN, LAG, false, true, false>(a, r);
+        else if (r.cens) launch_classed<KID, DYN, LAG, true, true, true>(a, r);
+        else launch_classed<KID, DYN, LAG, true, true, false>(a, r);
+      }
+      break;
+    case R_STEPS:
+      if constexpr (!DYN && !LAG) {
+        if (r.ll)
+          hipLaunchKernelGGL((pmx_analytical_steps<KID, true>), grid, block, 0, st, a.m, a.ops, a.steps, a.theta, a.P, r.n, r.s_chunk,
+                             r.n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status);
         else
-          hipLaunchKernelGGL((pmx_analytical_steps<KID, false>), dim3(static_cast<uint32_t>(blocks)), dim3(threads), 0, st, a.m, a.ops,
-                             a.steps, a.theta, a.P, n_walk, s_chunk, n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status);
-        return hipGetLastError();
+          hipLaunchKernelGGL((pmx_analytical_steps<KID, false>), grid, block, 0, st, a.m, a.ops, a.steps, a.theta, a.P, r.n, r.s_chunk,
+                             r.n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status);
       }
-    }
-    if constexpr (DYN && !LAG && kHasDirect0<kernel_structure(KID)>) {
-      if (a.no_rates && a.m.pm == 0) {  // three-compartment covariate model, no infusion anywhere: the matrix-free walker
-        *name = (list != nullptr) ? *name : "pmx_analytical_dyn3";
-        const size_t lds3 = (a.prop_slots > 0) ? static_cast<size_t>(a.prop_slots) * LaneModel<KID>::S::ND0 * sizeof(double) * threads : 0;
-        const bool ll = a.ops.ll_obs != nullptr, er = a.eig_reuse != 0;
+      break;
+    case R_DYN3:
+      if constexpr (DYN && !LAG && kHasDirect0<kernel_structure(KID)>) {
         auto go = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(blocks)), dim3(threads), lds3, st, a.m, a.ops, a.theta, a.P, n_walk,
-                             s_chunk, n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status, a.prop_slots);
+          hipLaunchKernelGGL(kern, grid, block, r.lds, st, a.m, a.ops, a.theta, a.P, r.n, r.s_chunk, r.n_ptiles, a.pred, a.ld,
+                             a.status, list, a.cls.zero_status, a.prop_slots);
         };
-        if (ll && er) go(pmx_analytical_dyn3<KID, true, true>);
-        else if (ll) go(pmx_analytical_dyn3<KID, true, false>);
-        else if (er) go(pmx_analytical_dyn3<KID, false, true>);
+        if (r.ll && r.eig_reuse) go(pmx_analytical_dyn3<KID, true, true>);
+        else if (r.ll) go(pmx_analytical_dyn3<KID, true, false>);
+        else if (r.eig_reuse) go(pmx_analytical_dyn3<KID, false, true>);
         else go(pmx_analytical_dyn3<KID, false, false>);
-        return hipGetLastError();
       }
-    }
-    if (a.ops.ll_obs != nullptr)
-      hipLaunchKernelGGL((pmx_analytical_grid<KID, DYN, LAG, true>), dim3(static_cast<uint32_t>(blocks)), dim3(threads), lds, st,
-                         a.m, a.ops, a.theta, a.P, n_walk, s_chunk, n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status,
-                         a.prop_slots);
-    else
-      hipLaunchKernelGGL((pmx_analytical_grid<KID, DYN, LAG, false>), dim3(static_cast<uint32_t>(blocks)), dim3(threads), lds, st,
-                         a.m, a.ops, a.theta, a.P, n_walk, s_chunk, n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status,
-                         a.prop_slots);
-  } else {
-    *name = kNamePair;
-    const int64_t n_pairs = a.batch ? a.S : a.S * a.P;
-    const int64_t blocks = (n_pairs + kBlock - 1) / kBlock;
-    if (a.ops.ll_obs != nullptr)
-      hipLaunchKernelGGL((pmx_analytical_pair<KID, DYN, LAG, true>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, st,
-                         a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred, a.ld, a.status);
-    else
-      hipLaunchKernelGGL((pmx_analytical_pair<KID, DYN, LAG, false>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, st,
-                         a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred, a.ld, a.status);
+      break;
+    case R_GRID:
+      if (r.ll)
+        hipLaunchKernelGGL((pmx_analytical_grid<KID, DYN, LAG, true>), grid, block, r.lds, st, a.m, a.ops, a.theta, a.P, r.n, r.s_chunk,
+                           r.n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status, a.prop_slots);
+      else
+        hipLaunchKernelGGL((pmx_analytical_grid<KID, DYN, LAG, false>), grid, block, r.lds, st, a.m, a.ops, a.theta, a.P, r.n, r.s_chunk,
+                           r.n_ptiles, a.pred, a.ld, a.status, list, a.cls.zero_status, a.prop_slots);
+      break;
+    case R_PAIR:
+      if (r.ll)
+        hipLaunchKernelGGL((pmx_analytical_pair<KID, DYN, LAG, true>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch,
+                           a.pred, a.ld, a.status);
+      else
+        hipLaunchKernelGGL((pmx_analytical_pair<KID, DYN, LAG, false>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch,
+                           a.pred, a.ld, a.status);
+      break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
 template <int MODEL, bool LAG, bool LL, bool ADAPT>
-hipError_t launch_ode_v(const LaunchArgs& a, const char** name) {
+hipError_t launch_ode_v(const LaunchArgs& a, const Route& r) {
   hipStream_t st = static_cast<hipStream_t>(a.stream);
-  if (a.mode == MODE_GRID) {
-    *name = ADAPT ? (LAG ? "pmx_ode_dopri5_grid<lag>" : "pmx_ode_dopri5_grid") : (LAG ? "pmx_ode_rk4_grid<lag>" : "pmx_ode_rk4_grid");
-    if (ADAPT && a.m.ode_stiff) *name = LAG ? "pmx_ode_ros2_grid<lag>" : "pmx_ode_ros2_grid";
-    const int64_t n_chunks = (a.S + a.s_chunk - 1) / a.s_chunk;
-    const int64_t blocks = n_chunks * a.n_ptiles;
-    hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, ADAPT>), dim3(static_cast<uint32_t>(blocks)), dim3(grid_threads(a.P)), 0, st,
-                       a.m, a.ops, a.theta, a.P, a.S, a.s_chunk, a.n_ptiles, a.pred, a.ld, a.status);
-  } else {
-    *name = ADAPT ? (LAG ? "pmx_ode_dopri5_pair<lag>" : "pmx_ode_dopri5_pair") : (LAG ? "pmx_ode_rk4_pair<lag>" : "pmx_ode_rk4_pair");
-    if (ADAPT && a.m.ode_stiff) *name = LAG ? "pmx_ode_ros2_pair<lag>" : "pmx_ode_ros2_pair";
-    const int64_t n_pairs = a.batch ? a.S : a.S * a.P;
-    const int64_t blocks = (n_pairs + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, ADAPT>), dim3(static_cast<uint32_t>(blocks)), dim3(kBlock), 0, st,
-                       a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred, a.ld, a.status);
-  }
+  const dim3 grid(static_cast<uint32_t>(r.blocks)), block(r.threads);
+  if (r.mode == MODE_GRID)
+    hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, ADAPT>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, r.s_chunk,
+                       r.n_ptiles, a.pred, a.ld, a.status);
+  else
+    hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, ADAPT>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred,
+                       a.ld, a.status);
   return hipGetLastError();
 }
 
 template <int MODEL>
-hipError_t launch_ode(const LaunchArgs& a, const char** name) {
-  const bool lag = a.m.n_lag_slots > 0, ll = a.ops.ll_obs != nullptr, ad = a.adaptive != 0;
-  if (lag) {
-    if (ll) return ad ? launch_ode_v<MODEL, true, true, true>(a, name) : launch_ode_v<MODEL, true, true, false>(a, name);
-    return ad ? launch_ode_v<MODEL, true, false, true>(a, name) : launch_ode_v<MODEL, true, false, false>(a, name);
+hipError_t launch_ode(const LaunchArgs& a, const Route& r) {
+  const bool ad = r.solver != 0;  // (the same instantiation serves both adaptive steppers: DevModel::ode_stiff)
+  if (r.lag) {
+    if (r.ll) return ad ? launch_ode_v<MODEL, true, true, true>(a, r) : launch_ode_v<MODEL, true, true, false>(a, r);
+    return ad ? launch_ode_v<MODEL, true, false, true>(a, r) : launch_ode_v<MODEL, true, false, false>(a, r);
   }
-  if (ll) return ad ? launch_ode_v<MODEL, false, true, true>(a, name) : launch_ode_v<MODEL, false, true, false>(a, name);
-  return ad ? launch_ode_v<MODEL, false, false, true>(a, name) : launch_ode_v<MODEL, false, false, false>(a, name);
+  if (r.ll) return ad ? launch_ode_v<MODEL, false, true, true>(a, r) : launch_ode_v<MODEL, false, true, false>(a, r);
+  return ad ? launch_ode_v<MODEL, false, false, true>(a, r) : launch_ode_v<MODEL, false, false, false>(a, r);
 }
 
 template <int KID>
-hipError_t launch_analytical_k(const LaunchArgs& a, const char** name) {
-  if (a.m.n_lag_slots > 0) return launch_analytical<KID, false, true>(a, name);  // (lag + covariate-derived constants is rejected at model_create)
-  return a.dyn ? launch_analytical<KID, true, false>(a, name) : launch_analytical<KID, false, false>(a, name);
+hipError_t launch_analytical_k(const LaunchArgs& a, const Route& r) {
+  if (r.lag) return launch_analytical<KID, false, true>(a, r);  // (lag + covariate-derived constants is rejected at model_create)
+  return r.dyn ? launch_analytical<KID, true, false>(a, r) : launch_analytical<KID, false, false>(a, r);
 }
 
 }  // namespace
@@ -2291,33 +2206,33 @@ extern "C" int32_t pmx_debug_ll_stamps(uint64_t* out5, int32_t reset) {  // diag
 namespace pmx {
 #endif
 
-hipError_t launch_predict(const LaunchArgs& a, const char** name) {
+hipError_t launch_route(const LaunchArgs& a, const Route& r) {
   if (a.S <= 0 || (a.P <= 0 && !a.batch)) return hipSuccess;
   if (a.m.eq_kind == PMX_EQ_ANALYTICAL) {
     switch (a.m.kernel) {
-      case 0: return launch_analytical_k<0>(a, name);
-      case 1: return launch_analytical_k<1>(a, name);
-      case 2: return launch_analytical_k<2>(a, name);
-      case 3: return launch_analytical_k<3>(a, name);
-      case 4: return launch_analytical_k<4>(a, name);
-      case 5: return launch_analytical_k<5>(a, name);
-      case 6: return launch_analytical_k<6>(a, name);
-      case 7: return launch_analytical_k<7>(a, name);
-      case 8: return launch_analytical_k<8>(a, name);
-      case 9: return launch_analytical_k<9>(a, name);
-      case 10: return launch_analytical_k<10>(a, name);
-      case 11: return launch_analytical_k<11>(a, name);
+      case 0: return launch_analytical_k<0>(a, r);
+      case 1: return launch_analytical_k<1>(a, r);
+      case 2: return launch_analytical_k<2>(a, r);
+      case 3: return launch_analytical_k<3>(a, r);
+      case 4: return launch_analytical_k<4>(a, r);
+      case 5: return launch_analytical_k<5>(a, r);
+      case 6: return launch_analytical_k<6>(a, r);
+      case 7: return launch_analytical_k<7>(a, r);
+      case 8: return launch_analytical_k<8>(a, r);
+      case 9: return launch_analytical_k<9>(a, r);
+      case 10: return launch_analytical_k<10>(a, r);
+      case 11: return launch_analytical_k<11>(a, r);
       default: return hipErrorInvalidValue;
     }
   }
   switch (a.m.kernel) {
-    case PMX_ODE_ONE_CMT_IV: return launch_ode<PMX_ODE_ONE_CMT_IV>(a, name);
-    case PMX_ODE_ONE_CMT_ORAL: return launch_ode<PMX_ODE_ONE_CMT_ORAL>(a, name);
-    case PMX_ODE_TWO_CMT_IV: return launch_ode<PMX_ODE_TWO_CMT_IV>(a, name);
-    case PMX_ODE_TWO_CMT_ORAL: return launch_ode<PMX_ODE_TWO_CMT_ORAL>(a, name);
-    case PMX_ODE_THREE_CMT_IV: return launch_ode<PMX_ODE_THREE_CMT_IV>(a, name);
-    case PMX_ODE_THREE_CMT_ORAL: return launch_ode<PMX_ODE_THREE_CMT_ORAL>(a, name);
-    case PMX_ODE_ONE_CMT_MM: return launch_ode<PMX_ODE_ONE_CMT_MM>(a, name);
+    case PMX_ODE_ONE_CMT_IV: return launch_ode<PMX_ODE_ONE_CMT_IV>(a, r);
+    case PMX_ODE_ONE_CMT_ORAL: return launch_ode<PMX_ODE_ONE_CMT_ORAL>(a, r);
+    case PMX_ODE_TWO_CMT_IV: return launch_ode<PMX_ODE_TWO_CMT_IV>(a, r);
+    case PMX_ODE_TWO_CMT_ORAL: return launch_ode<PMX_ODE_TWO_CMT_ORAL>(a, r);
+    case PMX_ODE_THREE_CMT_IV: return launch_ode<PMX_ODE_THREE_CMT_IV>(a, r);
+    case PMX_ODE_THREE_CMT_ORAL: return launch_ode<PMX_ODE_THREE_CMT_ORAL>(a, r);
+    case PMX_ODE_ONE_CMT_MM: return launch_ode<PMX_ODE_ONE_CMT_MM>(a, r);
     default: return hipErrorInvalidValue;
   }
 }

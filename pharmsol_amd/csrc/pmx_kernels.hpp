@@ -59,6 +59,39 @@ struct DevSteps {
 
 enum LaneMode : int32_t { MODE_GRID = 0, MODE_PAIR = 1 };
 
+// Which kernel serves (part of) a launch, with which template variant and which geometry.  pmx_launch.cpp decides all
+// of it (plan_routes) and names it (route_name); the launchers of pmx_kernels.hip only switch on it.
+enum RouteFamily : int32_t {
+  R_CLASSED,       // pmx_analytical_classed: exact or loose classes
+  R_CLASSED_LL,    // pmx_analytical_classed_ll: exact classes of a plain model, log-likelihood
+  R_STEPS,         // pmx_analytical_steps: the lean walker over fused step records
+  R_DYN3,          // pmx_analytical_dyn3: the matrix-free three-compartment covariate walker
+  R_GRID,          // pmx_analytical_grid: the generic walker
+  R_PAIR,          // pmx_analytical_pair
+  R_ODE,           // pmx_ode_rk4_grid / _pair (mode): built-in diffeq bodies
+  R_JIT_ANALYTICAL, R_JIT_ODE, R_JIT_ODE_USER,  // run-time-compiled models (mode)
+  R_STATIC_AGRID   // the PMX_DEBUG_STATIC_SO experiment hook
+};
+struct Route {
+  int32_t family;   // RouteFamily
+  int32_t mode;     // LaneMode
+  bool ll;          // log-likelihood variant
+  bool cens;        // ... of a population with censored observations / residual error models (classed kernels' CENS)
+  bool loose;       // classed: the loose chunks (per-member step lengths)
+  bool lag, dyn;    // lagged input / kernel parameters depend on covariates (re-prepare per PROP)
+  bool eig_reuse;   // dyn3: the stream marks segments that repeat the previous built segment's rate constants (EIGR)
+  bool leftover;    // walkers behind a classed launch: the subjects of cls.generic_subjects instead of 0..S-1
+  int32_t solver;   // ODE: 0 = RK4, 1 = DOPRI5, 2 = ROS2
+  int64_t n;        // walkers: subjects walked; classed: chunks served
+  int32_t s_chunk;  // GRID walkers: subjects walked by one block
+  int32_t n_ptiles; // GRID: ceil(P / threads)
+  int32_t cpb;      // classed: chunks per block
+  uint32_t threads;
+  int64_t blocks;
+  size_t lds;       // dynamic LDS bytes (kept propagators)
+  const char* name; // route_name(*this): what pmx_last_kernel_name reports when this route lends its name
+};
+
 struct LaunchArgs {
   DevModel m;
   DevOps ops;
@@ -67,24 +100,10 @@ struct LaunchArgs {
   double* pred;
   int64_t ld;
   uint8_t* status;
-  int32_t mode;      // LaneMode
-  int32_t batch;     // PAIR only: subject s uses theta row s
-  int32_t s_chunk;   // GRID: subjects walked by one block
-  int32_t n_ptiles;  // GRID: ceil(P / 256)
-  int32_t dyn;       // analytical: kernel parameters depend on covariates (re-prepare per PROP)
-  int32_t adaptive;     // ODE: PMX_SOLVER_DOPRI5
-  int32_t ll_censored;  // log-likelihood mode: the population holds censored observations (classed kernel's CENS variant)
-  int32_t use_classes;  // GRID analytical: run the classed kernel on cls.n_chunks, the generic one on the rest
+  int32_t batch;        // PAIR only: subject s uses theta row s
   int32_t prop_slots;   // DYN GRID: LDS slots for kept propagators (OpStream::prop_cache_used; 0 = none)
-  int32_t dyn_tile;     // DYN GRID with kept propagators: support points per block (0 = the default tile)
-  int32_t no_rates;     // the compiled stream holds no PROP with an active infusion (three-compartment DYN: matrix-free walker)
-  int32_t eig_reuse;    // ... and marks segments that repeat the previous built segment's rate constants (bit 27: the EIGR variant)
-  int32_t tune_cpb;     // > 0: chunks per block of the classed kernel forced by PMX_TUNE_CPB (tuning experiments)
-  int32_t tune_ll_old;  // != 0: PMX_TUNE_LL_OLD - the round-2 log-likelihood kernel for exact classes (A/B)
   DevClassPlan cls;
-  DevSteps steps;       // analytical GRID, plain models (no covariate factors, no lag, no pm_ indexing): nullptr = none
-  const int32_t* subj_list;  // GRID: walk these subjects instead of 0..S-1 (nullptr = all)
-  int64_t n_list;
+  DevSteps steps;       // fused step records of the lean walker (R_STEPS)
   void* stream;
 };
 
@@ -124,7 +143,7 @@ hipError_t launch_status_any(const uint8_t* d_status, int64_t n, int32_t* d_flag
 // a linear streaming fill of n_doubles (pmx_measure_write_ceiling)
 hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape = 0);  // shape 0..2 (pmx_kernels.hip)
 
-// Enqueue the prediction kernel; *name receives a static string naming the kernel family.
-hipError_t launch_predict(const LaunchArgs& a, const char** name);
+// Enqueue the kernel of one route (a library kernel: not the R_JIT_* / R_STATIC_AGRID families).
+hipError_t launch_route(const LaunchArgs& a, const Route& r);
 
 }  // namespace pmx

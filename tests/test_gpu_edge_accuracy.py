@@ -177,7 +177,7 @@ def test_loose_classes(group, env):
 
 @pytest.mark.parametrize("group", LAG, ids=ids(LAG))
 def test_lag_walkers(group, env):
-    # (no ladder run: the host never builds the exponential ladder for a model with a lagged input, pmx_api.cpp key_for)
+    # (no ladder run: the host never builds the exponential ladder for a model with a lagged input, pmx_launch.cpp key_for)
     m, flat, truth = group_population(group)
     env()
     check(group, m, flat, truth, cycle(group, 64), "pmx_analytical_classed<lag>")
