@@ -7,7 +7,9 @@ LIB := pharmsol_amd/lib/libpmx_hip.so
 # lines (slope*t + intercept) exactly like the reference; device code keeps FMA contraction.
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
-OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(CSRC)/build/pmx_kernels.o $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
+# the kernel units: one translation unit per kernel family (pmx_lanes.hpp lists them)
+KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util
+OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 
 all: $(LIB) oracle
@@ -22,9 +24,17 @@ $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o: $
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -x hip -c $< -o $@
 
-$(CSRC)/build/pmx_kernels.o: $(CSRC)/pmx_kernels.hip $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
+KHDR := $(CSRC)/pmx_lanes.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
+$(CSRC)/build/%.o: $(CSRC)/%.hip $(KHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@
+
+# a kernel unit's device assembly, same flags (tools/isa_guard.py, isa_count.sh, isa_of.py, kernel_resources.py); `make asm`: all units
+$(CSRC)/build/%.s: $(CSRC)/%.hip $(KHDR)
+	@mkdir -p $(CSRC)/build
+	$(HIPCC) $(DEVFLAGS) --cuda-device-only -S $< -o $@
+
+asm: $(KUNITS:%=$(CSRC)/build/%.s)
 
 # the device headers a run-time (hiprtc) compile of a user model includes, embedded as string literals
 $(CSRC)/build/pmx_jit_headers.inc: $(DEVHDR) tools/embed_headers.py
@@ -52,7 +62,7 @@ oracle:
 clean:
 	rm -rf $(CSRC)/build pharmsol_amd/lib oracle/_build
 
-.PHONY: all oracle clean
+.PHONY: all oracle clean asm
 
 # C++ host-facade test binary (links the product library and, as the checker, the CPU oracle)
 tests/cpp/facade_test: tests/cpp/facade_test.cpp include/pharmsol_hip.hpp include/pmx.h $(LIB) oracle

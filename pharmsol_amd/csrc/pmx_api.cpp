@@ -1015,7 +1015,7 @@ int32_t pmx_measure_write_ceiling(double* d_buf, int64_t n_doubles, int32_t reps
   PMX_HIP(hipEventCreate(&e1));
   hipError_t e = hipSuccess;
   float best_ms = 0.0f;
-  for (int shape = 0; shape < 4 && e == hipSuccess; ++shape) {  // the best of four store shapes (pmx_kernels.hip)
+  for (int shape = 0; shape < 4 && e == hipSuccess; ++shape) {  // the best of four store shapes (pmx_util.hip)
     e = pmx::launch_fill_linear(d_buf, n_doubles, 0.0, stream, shape);  // untimed
     if (e == hipSuccess) e = hipEventRecord(e0, st);
     for (int32_t i = 0; i < reps && e == hipSuccess; ++i) e = pmx::launch_fill_linear(d_buf, n_doubles, 0.0, stream, shape);

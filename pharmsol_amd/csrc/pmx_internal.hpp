@@ -107,7 +107,7 @@ struct DeviceStream {
   pmx::DevClassPlan cls{};
   pmx::DevSteps steps{};  // fused step programs of the lean generic walker (analytical streams without lag / covariates)
   // Sigma tables of the log-likelihood, per set of error models.  They are filled ON THE DEVICE
-  // (pmx_kernels.hip pmx_ll_prepare_*), stream-ordered before the kernel that reads them: an optimiser that changes
+  // (pmx_util.hip pmx_ll_prepare_*), stream-ordered before the kernel that reads them: an optimiser that changes
   // gamma / lambda every call pays two ~10 us kernels, not a host pass over every observation plus a 40 MB upload.
   // A small LRU of slots; uses of one slot are chained through its event so that a slot is never rewritten while a
   // kernel on another stream still reads it.

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pmx_compile.hpp"
 #include "pmx_devtypes.hpp"
@@ -60,7 +61,7 @@ struct DevSteps {
 enum LaneMode : int32_t { MODE_GRID = 0, MODE_PAIR = 1 };
 
 // Which kernel serves (part of) a launch, with which template variant and which geometry.  pmx_launch.cpp decides all
-// of it (plan_routes) and names it (route_name); the launchers of pmx_kernels.hip only switch on it.
+// of it (plan_routes) and names it (route_name); the launch_<family> entries of the kernel units only switch on it.
 enum RouteFamily : int32_t {
   R_CLASSED,       // pmx_analytical_classed: exact or loose classes
   R_CLASSED_LL,    // pmx_analytical_classed_ll: exact classes of a plain model, log-likelihood
@@ -141,9 +142,40 @@ hipError_t launch_ll_prepare(const LLPrepareArgs& a);
 hipError_t launch_status_any(const uint8_t* d_status, int64_t n, int32_t* d_flag, void* stream);
 
 // a linear streaming fill of n_doubles (pmx_measure_write_ceiling)
-hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape = 0);  // shape 0..2 (pmx_kernels.hip)
+hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape = 0);  // shape 0..3 (pmx_util.hip)
 
-// Enqueue the kernel of one route (a library kernel: not the R_JIT_* / R_STATIC_AGRID families).
+// One entry per kernel family, at the end of the family's translation unit (pmx_grid.hip, pmx_classed.hip, ...): it
+// switches on the model's kernel id and the route's variant flags and enqueues that instantiation.  Policy-free: which
+// family, which variant and which geometry is the route's (pmx_launch.cpp plan_routes).
+hipError_t launch_classed(const LaunchArgs& a, const Route& r);
+hipError_t launch_classed_ll(const LaunchArgs& a, const Route& r);
+hipError_t launch_steps(const LaunchArgs& a, const Route& r);
+hipError_t launch_dyn3(const LaunchArgs& a, const Route& r);
+hipError_t launch_grid(const LaunchArgs& a, const Route& r);
+hipError_t launch_pair(const LaunchArgs& a, const Route& r);
+hipError_t launch_ode(const LaunchArgs& a, const Route& r);  // (r.mode: grid / pair)
+
+// Enqueue the kernel of one route (a library kernel: not the R_JIT_* / R_STATIC_AGRID families; pmx_launch.cpp).
 hipError_t launch_route(const LaunchArgs& a, const Route& r);
+
+// Run-time flags -> template arguments: dispatch(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), so a launch
+// is written once for all its variants.  with_kid does the same for the analytical kernel id (an unknown one: error).
+template <class F>
+hipError_t dispatch(F&& f) {
+  return f();
+}
+template <class F, class... Rest>
+hipError_t dispatch(F&& f, bool b, Rest... rest) {
+  if (b) return dispatch([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+  return dispatch([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+template <int K = 0, class F>
+hipError_t with_kid(int32_t kernel, F&& f) {
+  if constexpr (K < 12) {
+    return kernel == K ? f(std::integral_constant<int, K>{}) : with_kid<K + 1>(kernel, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
 
 }  // namespace pmx

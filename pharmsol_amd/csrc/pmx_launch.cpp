@@ -509,6 +509,21 @@ pmx::LaunchArgs launch_args(const pmx_model* model, const pmx_population* pop, c
 
 }  // namespace
 
+// a library kernel's route -> the entry of its family's translation unit
+hipError_t pmx::launch_route(const pmx::LaunchArgs& a, const pmx::Route& r) {
+  if (a.S <= 0 || (a.P <= 0 && !a.batch)) return hipSuccess;
+  switch (r.family) {
+    case pmx::R_CLASSED: return pmx::launch_classed(a, r);
+    case pmx::R_CLASSED_LL: return pmx::launch_classed_ll(a, r);
+    case pmx::R_STEPS: return pmx::launch_steps(a, r);
+    case pmx::R_DYN3: return pmx::launch_dyn3(a, r);
+    case pmx::R_GRID: return pmx::launch_grid(a, r);
+    case pmx::R_PAIR: return pmx::launch_pair(a, r);
+    case pmx::R_ODE: return pmx::launch_ode(a, r);  // (r.mode: grid / pair)
+    default: return hipErrorInvalidValue;
+  }
+}
+
 int32_t enqueue(const pmx_model* model, pmx_population* pop, const double* d_theta, int64_t P, int batch, double* d_pred,
                 int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq, int state_override) {
   const pmx_model_desc& d = model->d;

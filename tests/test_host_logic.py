@@ -294,7 +294,7 @@ def test_prediction_stores_of_the_write_bound_kernels_stay_fire_and_forget():
     the emit path (a rarely taken branch leaving a vector load pending at a join did it once: C3 0.83 -> 0.98 ms) makes
     every observation step wait for all earlier prediction stores.  The compiled assembly of every exact / loose prediction
     instantiation of the classed kernel must have no vmcnt wait in a block that holds a 16-byte prediction store.
-    (Compiles pmx_kernels.hip to assembly once - about 90 s - and reuses it while the sources do not change.)"""
+    (Compiles pmx_classed.hip to assembly once - about 70 s - and reuses it while the sources do not change.)"""
     import importlib.util
     import os
 

@@ -1,13 +1,13 @@
 #!/bin/bash
-# Count VALU instructions per kernel of pmx_kernels.hip (whole function; compare before/after a change).
-# usage: tools/isa_count.sh [out.s]   (writes the gfx950 assembly there, default /tmp/pmx_kernels.s)
-out=${1:-/tmp/pmx_kernels.s}
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-parameter -Iinclude --cuda-device-only -S \
-  pharmsol_amd/csrc/pmx_kernels.hip -o "$out" || exit 1
-python3 - "$out" <<'PY'
+# Count VALU instructions per kernel (whole function; compare before/after a change).
+# usage: tools/isa_count.sh [unit ...]   (kernel units such as pmx_classed; default: all.  The gfx950 assembly is the
+# Makefile's: pharmsol_amd/csrc/build/<unit>.s)
+b=pharmsol_amd/csrc/build
+if [ $# -eq 0 ]; then make -s asm || exit 1; set -- $b/pmx_*.s; else set -- "${@/#/$b/}"; set -- "${@/%/.s}"; make -s "$@" || exit 1; fi
+python3 - "$@" <<'PY'
 import re, subprocess, sys
 name, rows = None, {}
-for line in open(sys.argv[1]):
+for line in (l for p in sys.argv[1:] for l in open(p)):
     m = re.match(r"^(_Z\S+):", line)
     if m:
         name = m.group(1); rows[name] = [0, 0, 0, 0]; continue

@@ -4,28 +4,21 @@
 On gfx9-class hardware loads and stores share ONE in-order counter (vmcnt), so a single `s_waitcnt vmcnt(..)` that the
 compiler places in the emit path - e.g. because a rarely taken branch left a vector load pending at a join - makes every
 observation step wait for all earlier prediction stores.  That cost the C3 headline 15 % once this round (0.83 -> 0.98 ms)
-without changing one line of the hot loop's source.  This script compiles pmx_kernels.hip to assembly and checks, for
-every exact and loose prediction instantiation of pmx_analytical_classed, that no basic block holding a 16-byte
-prediction store also holds a vmcnt wait.
-usage: tools/isa_guard.py [path/to/pmx_kernels.s]   (compiles to pharmsol_amd/csrc/build/pmx_kernels.s when absent/stale)"""
+without changing one line of the hot loop's source.  This script has the Makefile compile pmx_classed.hip to assembly and
+checks, for every exact and loose prediction instantiation of pmx_analytical_classed, that no basic block holding a
+16-byte prediction store also holds a vmcnt wait.
+usage: tools/isa_guard.py [path/to/pmx_classed.s]   (default: pharmsol_amd/csrc/build/pmx_classed.s, made when absent/stale)"""
 import os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "pharmsol_amd", "csrc", "pmx_kernels.hip")
-OUT = os.path.join(ROOT, "pharmsol_amd", "csrc", "build", "pmx_kernels.s")
+OUT = "pharmsol_amd/csrc/build/pmx_classed.s"
 
 
 def assembly(path=None):
     if path:
         return open(path).read()
-    deps = [SRC] + [os.path.join(ROOT, "pharmsol_amd", "csrc", h) for h in
-                    ("pmx_structures.hpp", "pmx_device.hpp", "pmx_devtypes.hpp", "pmx_ode.hpp", "pmx_kernels.hpp")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-parameter",
-                        "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", SRC, "-o", OUT], check=True,
-                       stderr=subprocess.DEVNULL)
-    return open(OUT).read()
+    subprocess.run(["make", "-s", "-C", ROOT, OUT], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return open(os.path.join(ROOT, OUT)).read()
 
 
 def check(text):

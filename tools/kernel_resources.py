@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Print VGPR/SGPR/scratch/occupancy per kernel of pmx_kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: tools/kernel_resources.py [substring-filter]"""
+"""Print VGPR/SGPR/scratch/occupancy per kernel (the remarks of -Rpass-analysis=kernel-resource-usage, added to the
+Makefile's DEVFLAGS for a fresh compile of the kernel units' assembly).
+usage: tools/kernel_resources.py [substring-filter [unit ...]]   (kernel units such as pmx_classed; default: all)"""
 import re, subprocess, sys
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
-src = "pharmsol_amd/csrc/pmx_kernels.hip"
-out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-parameter", "-Iinclude",
-                      "-c", src, "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
+targets = ["pharmsol_amd/csrc/build/%s.s" % u for u in sys.argv[2:]] or ["asm"]
+flags = subprocess.run(["make", "-s", "--eval", "print-devflags: ; @echo $(DEVFLAGS)", "print-devflags"], capture_output=True, text=True,
+                       check=True).stdout.strip()
+out = subprocess.run(["make", "-s", "-B", "-j8", "-Otarget", "DEVFLAGS=" + flags + " -Rpass-analysis=kernel-resource-usage"] + targets,
+                     capture_output=True, text=True, check=True).stderr
 rows, cur = [], None
 pats = (("vgpr", r" VGPRs: (\d+)"), ("sgpr", r"TotalSGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
         ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
