@@ -66,6 +66,18 @@ pub fn verify_abi() -> Result<(), PharmsolError> {
     }
 }
 
+/// Counters of the code-object cache in front of hiprtc (include/pmx.h "code-object cache"): compiles, hits per level,
+/// files written / refused, what the memory level holds.
+pub fn jit_cache_stats() -> Result<pmx_jit_cache_counters, PharmsolError> {
+    let mut c: pmx_jit_cache_counters = unsafe { std::mem::zeroed() };
+    check(unsafe { pmx_jit_cache_stats(&mut c) }).map(|_| c)
+}
+
+/// Empties the memory level and zeroes the counters; `disk`: also removes the cache files in PMX_JIT_CACHE_DIR.
+pub fn jit_cache_clear(disk: bool) {
+    unsafe { pmx_jit_cache_clear(disk as i32) }
+}
+
 // ------------------------------------------------------------------------------------------ flatten
 /// `Data` as the structure-of-arrays `pmx_population_desc` points into.  Owns the arrays; `desc()` borrows them.
 pub struct FlatData {

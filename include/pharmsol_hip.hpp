@@ -37,6 +37,10 @@ inline void check(int32_t rc, bool allow_pair_failures = false) {
   throw Error(rc, pmx_last_error());
 }
 
+// The code-object cache in front of hiprtc (pmx.h "code-object cache"): its counters, and emptying it.
+inline pmx_jit_cache_counters jit_cache_stats() { pmx_jit_cache_counters c{}; check(pmx_jit_cache_stats(&c)); return c; }
+inline void jit_cache_clear(bool disk = false) { pmx_jit_cache_clear(disk ? 1 : 0); }
+
 // ---------------------------------------------------------------- data model (src/data)
 struct Event {
   uint8_t kind;  // PMX_EV_*

@@ -499,6 +499,25 @@ int32_t pmx_debug_jit_source_user(const pmx_model_desc* desc, const char* source
 int32_t pmx_debug_jit_source(const pmx_model_desc* desc, const char* source, int32_t has_init, char** out_text);
 void pmx_free_text(char* text);
 
+/* ---- code-object cache of the run-time-compiled models (csrc/pmx_jit_cache.cpp; needs no device) ----------------
+ * Every hiprtc compile goes through a content-addressed cache: the key is a 128-bit hash of the whole translation
+ * unit, the embedded device headers, the option list, the target and the compiler's identity (version and library file).  The
+ * memory level is process-wide (PMX_JIT_CACHE_ENTRIES entries, 64 by default, least recently used out first); the disk
+ * level is active when PMX_JIT_CACHE_DIR names a directory; PMX_JIT_CACHE=0 switches both off.  A
+ * failed compile is never stored, and no cache failure fails a model creation.
+ *   compiles      hiprtc compiles run            disk_writes   cache files written
+ *   mem_hits      answered from memory           disk_rejects  cache files found but refused (truncated, corrupt, other key)
+ *   disk_hits     answered from a cache file     entries/bytes what the memory level holds now */
+typedef struct pmx_jit_cache_counters {
+  int64_t compiles, mem_hits, disk_hits, disk_writes, disk_rejects, entries, bytes;
+} pmx_jit_cache_counters;
+int32_t pmx_jit_cache_stats(pmx_jit_cache_counters* out);
+/* Empties the memory level and zeroes the counters; also_disk != 0: removes the cache's own files from PMX_JIT_CACHE_DIR. */
+void pmx_jit_cache_clear(int32_t also_disk);
+/* Compiles (or fetches from the cache) the big-lists build of a closure model now - what the first launch on a
+ * population with more than 64 lagged boluses in one occasion does.  PMX_OK and nothing done for any other model. */
+int32_t pmx_debug_jit_compile_big_lists(const pmx_model* model);
+
 /*   em   [model.nout] error model per output equation
  *   ll   [n_subjects x ld_ll], ll[s*ld_ll + p]  (the reference's Array2 (n_subjects, n_support); it stores
  *        that matrix column-major, matrix.rs:60 — same logical matrix, support point fastest here)

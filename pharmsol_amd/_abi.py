@@ -232,6 +232,11 @@ class pmx_op_stream_view(C.Structure):
 PMX_OP_RESET, PMX_OP_BOLUS, PMX_OP_OBS, PMX_OP_PROP = 0, 1, 2, 3
 
 
+class pmx_jit_cache_counters(C.Structure):
+    _fields_ = [("compiles", C.c_int64), ("mem_hits", C.c_int64), ("disk_hits", C.c_int64), ("disk_writes", C.c_int64),
+                ("disk_rejects", C.c_int64), ("entries", C.c_int64), ("bytes", C.c_int64)]
+
+
 class PmxError(RuntimeError):
     """A failed C-ABI call (the Python face of ``PharmsolError``, src/error/mod.rs:13-49)."""
 

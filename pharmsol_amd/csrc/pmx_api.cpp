@@ -97,6 +97,7 @@ int64_t pmx_sizeof_struct(const char* name) {
   PMX_SZ(pmx_model_desc)
   PMX_SZ(pmx_error_model)
   PMX_SZ(pmx_op_stream_view)
+  PMX_SZ(pmx_jit_cache_counters)
 #undef PMX_SZ
   return -1;
 }

@@ -34,6 +34,11 @@ struct Tunables {
   int32_t steps_per_trip = 0, grid_min_p = 0, cpb = 0;
   ClassTunables cls;
   int32_t prop_slots = -1, dyn_tile = 0;
+  // code-object cache (pmx_jit_cache.cpp): PMX_JIT_CACHE=0 off, PMX_JIT_CACHE_ENTRIES, PMX_JIT_CACHE_DIR (null: no disk
+  // level; the text is interned and never freed, so that a snapshot stays a plain copy)
+  bool jit_cache = true;
+  int32_t jit_cache_entries = 64;
+  const char* jit_cache_dir = nullptr;
   void load();
 };
 Tunables tunables();

@@ -4,6 +4,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <set>
 
 #include "pmx_internal.hpp"
 #include "pmx_structures.hpp"  // kernel_structure(), kernel_nparams(), Structure<ST>::Prop
@@ -40,6 +41,13 @@ void Tunables::load() {
   dyn_tile = num("PMX_TUNE_DYN_TILE");
   cls.spread = tri("PMX_TUNE_SPREAD");
   cls.loose = tri("PMX_TUNE_LOOSE");
+  jit_cache = tri("PMX_JIT_CACHE") != 0;
+  jit_cache_entries = num("PMX_JIT_CACHE_ENTRIES") > 0 ? num("PMX_JIT_CACHE_ENTRIES") : 64;  // (64: a policy choice, not a measurement)
+  {
+    static std::set<std::string> dirs;  // (load() runs under g_tun_mu)
+    const char* e = std::getenv("PMX_JIT_CACHE_DIR");
+    jit_cache_dir = (e && e[0]) ? dirs.insert(e).first->c_str() : nullptr;
+  }
 }
 
 namespace {
@@ -422,18 +430,26 @@ Routes plan_routes(const pmx_model& model, const StreamFacts& f, const Call& c, 
   return out;
 }
 
+// closure walkers keep 64 landing times per lane; an occasion with more takes the build with the scan path in
+// (model->jit_mu held)
+int32_t big_lists_code(const pmx_model* model) {
+  if (!model->jit_code_big.empty()) return PMX_OK;
+  pmx::JitSpec sp = model->jit_spec;
+  sp.big_lists = true;
+  std::string log;
+  if (!pmx::jit_compile(sp, &model->jit_code_big, &log))
+    return fail(PMX_ERR_HIP, "hiprtc could not compile the big-lists build of the model:\n" + log);
+  return PMX_OK;
+}
+
 // hiprtc-compiled model: its module on the population's device, loaded at first use
 int32_t jit_module(const pmx_model* model, const pmx_population* pop, const DeviceStream* ds, const pmx::JitModule** out) {
   const pmx_model_desc& d = model->d;
   std::lock_guard<std::mutex> lock(model->jit_mu);
-  // closure walkers keep 64 landing times per lane; an occasion with more takes the build with the scan path in
   const bool big = (d.eq_kind == PMX_EQ_ANALYTICAL || model->user_ode) && ds->f.max_lagb_per_list > pmx::kUserLagKept;
-  if (big && model->jit_code_big.empty()) {
-    pmx::JitSpec sp = model->jit_spec;
-    sp.big_lists = true;
-    std::string log;
-    if (!pmx::jit_compile(sp, &model->jit_code_big, &log))
-      return fail(PMX_ERR_HIP, "hiprtc could not compile the big-lists build of the model:\n" + log);
+  if (big) {
+    const int32_t rc = big_lists_code(model);
+    if (rc != PMX_OK) return rc;
   }
   auto& modules = big ? model->jit_modules_big : model->jit_modules;
   auto it = modules.find(pop->device);
@@ -508,6 +524,13 @@ pmx::LaunchArgs launch_args(const pmx_model* model, const pmx_population* pop, c
 }
 
 }  // namespace
+
+extern "C" int32_t pmx_debug_jit_compile_big_lists(const pmx_model* model) {
+  if (!model) return fail(PMX_ERR_INVALID_ARGUMENT, "model is null");
+  if (!model->custom || !(model->d.eq_kind == PMX_EQ_ANALYTICAL || model->user_ode)) return PMX_OK;
+  std::lock_guard<std::mutex> lock(model->jit_mu);
+  return big_lists_code(model);
+}
 
 // a library kernel's route -> the entry of its family's translation unit
 hipError_t pmx::launch_route(const pmx::LaunchArgs& a, const pmx::Route& r) {

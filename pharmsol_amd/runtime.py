@@ -207,6 +207,19 @@ def jit_translation_unit(model) -> str:
         L.pmx_free_text(out)
 
 
+def jit_cache_stats() -> dict:
+    """Counters of the code-object cache in front of hiprtc (``pmx_jit_cache_stats``): ``compiles``, ``mem_hits``,
+    ``disk_hits``, ``disk_writes``, ``disk_rejects``, and what the memory level holds now (``entries``, ``bytes``)."""
+    c = _abi.pmx_jit_cache_counters()
+    _ffi.check(_ffi.lib().pmx_jit_cache_stats(C.byref(c)))
+    return {name: int(getattr(c, name)) for name, _ in c._fields_}
+
+
+def jit_cache_clear(disk: bool = False) -> None:
+    """Empty the memory level and zero the counters; ``disk=True`` also removes the cache files in ``PMX_JIT_CACHE_DIR``."""
+    _ffi.lib().pmx_jit_cache_clear(1 if disk else 0)
+
+
 def _as_model(model) -> DeviceModel:
     if isinstance(model, DeviceModel):
         return model
