@@ -395,6 +395,23 @@ macro_rules! hip_backend {
 hip_backend!(HipAnalytical, PMX_EQ_ANALYTICAL, "`Analytical` (src/simulator/equation/analytical/mod.rs) whose population entries run on the GPU.");
 hip_backend!(HipOde, PMX_EQ_ODE, "`ODE` (src/simulator/equation/ode/mod.rs) whose population entries run on the GPU.");
 
+impl HipOde {
+    /// `from_desc` with the checked fixed-step solver: RK4 at `desc.rk4_h_max` whose first step of every integration
+    /// piece is also taken as two half steps; a support point whose Richardson error estimate exceeds
+    /// `atol + rtol |x|` fails with status `PMX_PAIR_STEP_TOO_COARSE` (NaN rows from that piece on, -inf in
+    /// `log_likelihood_batch`) instead of returning what an unstable step computes.  Every other pair gets plain RK4's numbers.
+    pub fn from_desc_checked(mut desc: pmx_model_desc, rtol: f64, atol: f64) -> Result<Self, PharmsolError> {
+        desc.ode_solver = PMX_SOLVER_RK4_CHECKED;
+        desc.ode_rtol = rtol;
+        desc.ode_atol = atol;
+        Self::from_desc(desc)
+    }
+    /// Did the checked solver refuse this pair?  (`status` as `estimate_predictions_matrix` returns it.)
+    pub fn step_too_coarse(status: u8) -> bool {
+        status as i32 == PMX_PAIR_STEP_TOO_COARSE
+    }
+}
+
 /// `AssayErrorModel::{Additive, Proportional}` (src/data/error_model.rs:786-812) as the library's record.
 pub fn assay_error_model(em: &crate::data::error_model::AssayErrorModel) -> Result<pmx_error_model, PharmsolError> {
     use crate::data::error_model::AssayErrorModel as A;

@@ -68,7 +68,10 @@ enum {
   PMX_PAIR_BAD_LAG = 3,       /* the support point gives a NaN lag time: its predictions are NaN (the reference panics in
                                  its sort).  A NEGATIVE lag is not an error: the bolus moves earlier, as in the reference
                                  (`if l != 0.0 { time += l }`, src/data/structs.rs:629-634) */
-  PMX_PAIR_SOLVER_FAIL = 4    /* adaptive ODE solver: step size underflow (PharmsolError::DiffsolError, error/mod.rs:25) */
+  PMX_PAIR_SOLVER_FAIL = 4,   /* adaptive ODE solver: step size underflow (PharmsolError::DiffsolError, error/mod.rs:25) */
+  PMX_PAIR_STEP_TOO_COARSE = 5 /* PMX_SOLVER_RK4_CHECKED: the step-doubling probe at the head of an integration piece found
+                                 that rk4_h_max does not resolve this support point's rates.  Rows from that piece on are
+                                 NaN, earlier rows keep their values.  Shorten rk4_h_max or take an adaptive solver. */
 };
 
 /* ---- events ---------------------------------------------------------------- */
@@ -225,13 +228,23 @@ typedef struct pmx_model_desc {
    * Dormand-Prince 5(4) with step-size control per lane: err = rms(e_i / (atol + rtol max(|x_i|, |x'_i|))) <= 1.
    * PMX_SOLVER_ROS2 = the stiff option (the role of the reference's default OdeSolver::Bdf / Sdirk, ode/mod.rs:60-77):
    * ROS2, a second-order L-stable Rosenbrock method with the same per-lane step control (error estimate from its embedded
-   * first-order solution), Jacobian by forward differences, NS x NS elimination in registers (csrc/pmx_ode.hpp ros2_try). */
+   * first-order solution), Jacobian by forward differences, NS x NS elimination in registers (csrc/pmx_ode.hpp ros2_try).
+   * PMX_SOLVER_RK4_CHECKED = the fixed-step walk of PMX_SOLVER_RK4 that refuses to lie: the first step of every
+   * integration piece (a PROP, or a sub-piece cut around a lagged bolus) is also taken as two half steps; Richardson's
+   * estimate e = 16/15 (x_half - x_full) of that step's local error, in the norm above, must be <= 1, else the pair is
+   * PMX_PAIR_STEP_TOO_COARSE.  A pair whose probes all pass gets plain RK4's numbers.  8 extra right-hand sides per
+   * piece.  Reads ode_rtol / ode_atol like the adaptive solvers. */
   int32_t ode_solver;
   int32_t reserved_;
   double ode_rtol, ode_atol;
 } pmx_model_desc;
 
-enum { PMX_SOLVER_RK4 = 0, PMX_SOLVER_DOPRI5 = 1, PMX_SOLVER_ROS2 = 2 /* stiff: L-stable Rosenbrock, adaptive */ };
+enum {
+  PMX_SOLVER_RK4 = 0,
+  PMX_SOLVER_DOPRI5 = 1,
+  PMX_SOLVER_ROS2 = 2,        /* stiff: L-stable Rosenbrock, adaptive */
+  PMX_SOLVER_RK4_CHECKED = 3  /* fixed-step RK4 with a step-doubling probe per piece (PMX_PAIR_STEP_TOO_COARSE) */
+};
 
 typedef struct pmx_population pmx_population; /* opaque */
 typedef struct pmx_model pmx_model;           /* opaque */

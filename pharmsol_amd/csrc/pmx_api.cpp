@@ -26,6 +26,10 @@ int ode_nparams(int model) {
   return (model >= 0 && model < PMX_ODE_MODEL_COUNT) ? n[model] : -1;
 }
 
+bool known_ode_solver(int32_t v) {
+  return v == PMX_SOLVER_RK4 || v == PMX_SOLVER_DOPRI5 || v == PMX_SOLVER_ROS2 || v == PMX_SOLVER_RK4_CHECKED;
+}
+
 // every pmx_model_create* ends here: the model's device-side description is fixed from now on
 int32_t publish(std::unique_ptr<pmx_model>& m, pmx_model** out) {
   finish_model(m.get());
@@ -264,10 +268,10 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     if (d->nstates < ode_nstates(d->kernel)) return fail(PMX_ERR_INVALID_ARGUMENT, "model has fewer states than its diffeq");
     if (d->nparams < ode_nparams(d->kernel)) return fail(PMX_ERR_INVALID_ARGUMENT, "too few parameters for the diffeq");
     if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-    if (d->ode_solver != PMX_SOLVER_RK4 && d->ode_solver != PMX_SOLVER_DOPRI5 && d->ode_solver != PMX_SOLVER_ROS2)
+    if (!known_ode_solver(d->ode_solver))
       return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
     if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-      return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solver needs ode_rtol > 0 and ode_atol > 0");
+      return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
     if (pm) return fail(PMX_ERR_INVALID_ARGUMENT, "pm_* indexing is a wrapper of the analytical structures (analytical/mod.rs:62-90): it does not apply to ODE models");
     if (d->n_bind != 0 && d->n_bind != ode_nparams(d->kernel))
       return fail(PMX_ERR_INVALID_ARGUMENT, "n_bind must equal the diffeq's parameter count");
@@ -340,6 +344,7 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     sp.ninputs = d->ndrugs > 0 ? d->ndrugs : 1;
     sp.has_init = m->has_init;
     sp.ncov = d->n_covariates;
+    sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
     sp.source = pmx::ode_descriptor_source(*d);
     std::string log;
     m->jit_spec = sp;
@@ -363,10 +368,10 @@ int32_t check_custom_desc(const pmx_model_desc* d, const char* source) {
   if (d->nout < 1 || d->nout > PMX_MAX_OUT) return fail(PMX_ERR_INVALID_ARGUMENT, "nout out of range");
   if (d->nparams < 1 || d->nparams > PMX_MAX_PARAMS) return fail(PMX_ERR_INVALID_ARGUMENT, "nparams out of range");
   if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-  if (d->ode_solver != PMX_SOLVER_RK4 && d->ode_solver != PMX_SOLVER_DOPRI5 && d->ode_solver != PMX_SOLVER_ROS2)
+  if (!known_ode_solver(d->ode_solver))
     return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
   if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solver needs ode_rtol > 0 and ode_atol > 0");
+    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
   if (d->n_covariates < 0 || d->n_covariates > PMX_MAX_COVARIATES)
     return fail(PMX_ERR_INVALID_ARGUMENT, "n_covariates out of range");
   if (d->n_derived != 0 || d->n_bind != 0 || d->pmetrics_indexing)
@@ -389,6 +394,7 @@ pmx::JitSpec spec_of(const pmx_model_desc* d, const char* source, int32_t has_in
   sp.ninputs = d->ndrugs > 0 ? d->ndrugs : 1;
   sp.has_init = has_init != 0;
   sp.ncov = d->n_covariates;
+  sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
   sp.source = source;
   return sp;
 }
@@ -501,9 +507,9 @@ int32_t check_user_ode(const pmx_model_desc* d, const char* source, uint32_t fns
   if (d->n_derived > 0 && !(fns & PMX_FN_DERIVE)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_derived > 0 needs PMX_FN_DERIVE (desc.derived[] is not read for user models)");
   if (d->n_bind != 0 || d->pmetrics_indexing) return fail(PMX_ERR_INVALID_ARGUMENT, "bind[] / pm indexing do not apply to ODE models with user closures");
   if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-  if (d->ode_solver != PMX_SOLVER_RK4 && d->ode_solver != PMX_SOLVER_DOPRI5 && d->ode_solver != PMX_SOLVER_ROS2) return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
+  if (!known_ode_solver(d->ode_solver)) return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
   if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solver needs ode_rtol > 0 and ode_atol > 0");
+    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
   for (int i = 0; i < PMX_MAX_INPUTS; ++i) {
     if (d->lag_param[i] >= d->nparams || d->fa_param[i] >= d->nparams)
       return fail(PMX_ERR_INVALID_ARGUMENT, "lag_param / fa_param out of range");
@@ -519,6 +525,7 @@ pmx::JitSpec user_spec_of(const pmx_model_desc* d, const char* source, uint32_t 
   sp.ode_user = d->eq_kind == PMX_EQ_ODE;
   sp.fns = fns;
   sp.desc = *d;
+  sp.checked = sp.ode_user && d->ode_solver == PMX_SOLVER_RK4_CHECKED;
   sp.source = source;
   return sp;
 }

@@ -172,8 +172,9 @@ pmx::CompileKey key_for(const pmx_model* m, const Tunables& tun, bool has_infusi
     k.rate_input = 0;
     for (int i = 0; i < PMX_MAX_INPUTS; ++i)
       if (m->d.lag_param[i] >= 0) k.lag_mask |= (1u << i);
-    // absolute piece times: a user body may be non-autonomous; the adaptive solver steps on [t0, t1] itself
-    k.want_times = m->custom || m->d.ode_solver != PMX_SOLVER_RK4;
+    // absolute piece times: a user body may be non-autonomous; the adaptive solver steps on [t0, t1] itself (checked RK4
+    // walks the fixed-step stream as it is)
+    k.want_times = m->custom || m->d.ode_solver == PMX_SOLVER_DOPRI5 || m->d.ode_solver == PMX_SOLVER_ROS2;
   }
   return k;
 }
@@ -243,17 +244,21 @@ static_launch_t static_launcher() {
 
 // THE name of a route: every string pmx_last_kernel_name can return is written here.
 const char* route_name(const Route& r) {
-  static const char* const kSolver[3][2][2] = {
+  static const char* const kSolver[4][2][2] = {
       {{"pmx_ode_rk4_grid", "pmx_ode_rk4_grid<lag>"}, {"pmx_ode_rk4_pair", "pmx_ode_rk4_pair<lag>"}},
       {{"pmx_ode_dopri5_grid", "pmx_ode_dopri5_grid<lag>"}, {"pmx_ode_dopri5_pair", "pmx_ode_dopri5_pair<lag>"}},
-      {{"pmx_ode_ros2_grid", "pmx_ode_ros2_grid<lag>"}, {"pmx_ode_ros2_pair", "pmx_ode_ros2_pair<lag>"}}};
-  static const char* const kJit[3][2][2] = {
+      {{"pmx_ode_ros2_grid", "pmx_ode_ros2_grid<lag>"}, {"pmx_ode_ros2_pair", "pmx_ode_ros2_pair<lag>"}},
+      {{"pmx_ode_rk4_checked_grid", "pmx_ode_rk4_checked_grid<lag>"}, {"pmx_ode_rk4_checked_pair", "pmx_ode_rk4_checked_pair<lag>"}}};
+  static const char* const kJit[4][2][2] = {
       {{"pmx_jit_ode_rk4_grid", "pmx_jit_ode_rk4_grid<lag>"}, {"pmx_jit_ode_rk4_pair", "pmx_jit_ode_rk4_pair<lag>"}},
       {{"pmx_jit_ode_dopri5_grid", "pmx_jit_ode_dopri5_grid<lag>"}, {"pmx_jit_ode_dopri5_pair", "pmx_jit_ode_dopri5_pair<lag>"}},
-      {{"pmx_jit_ode_ros2_grid", "pmx_jit_ode_ros2_grid<lag>"}, {"pmx_jit_ode_ros2_pair", "pmx_jit_ode_ros2_pair<lag>"}}};
-  static const char* const kUser[3][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
+      {{"pmx_jit_ode_ros2_grid", "pmx_jit_ode_ros2_grid<lag>"}, {"pmx_jit_ode_ros2_pair", "pmx_jit_ode_ros2_pair<lag>"}},
+      {{"pmx_jit_ode_rk4_checked_grid", "pmx_jit_ode_rk4_checked_grid<lag>"},
+       {"pmx_jit_ode_rk4_checked_pair", "pmx_jit_ode_rk4_checked_pair<lag>"}}};
+  static const char* const kUser[4][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
                                           {"pmx_jit_ode_user_dopri5_grid", "pmx_jit_ode_user_dopri5_pair"},
-                                          {"pmx_jit_ode_user_ros2_grid", "pmx_jit_ode_user_ros2_pair"}};
+                                          {"pmx_jit_ode_user_ros2_grid", "pmx_jit_ode_user_ros2_pair"},
+                                          {"pmx_jit_ode_user_rk4_checked_grid", "pmx_jit_ode_user_rk4_checked_pair"}};
   const int pair = r.mode == pmx::MODE_PAIR ? 1 : 0;
   switch (r.family) {
     case pmx::R_CLASSED:
@@ -392,8 +397,9 @@ Routes plan_routes(const pmx_model& model, const StreamFacts& f, const Call& c, 
   r.n = c.S;
   out.mode = r.mode;
   if (!analytical || model.custom) {
-    const bool adaptive = !analytical && d.ode_solver != PMX_SOLVER_RK4;
-    r.solver = adaptive ? (d.ode_solver == PMX_SOLVER_ROS2 ? 2 : 1) : 0;
+    // (Route::solver: the PMX_SOLVER_* values are the route's solver indices)
+    static_assert(PMX_SOLVER_RK4 == 0 && PMX_SOLVER_DOPRI5 == 1 && PMX_SOLVER_ROS2 == 2 && PMX_SOLVER_RK4_CHECKED == 3, "route_name");
+    r.solver = analytical ? 0 : d.ode_solver;
     r.lag = !analytical && !model.user_ode && model.dev.n_lag_slots > 0;
     r.family = !model.custom ? pmx::R_ODE : (analytical ? pmx::R_JIT_ANALYTICAL : (model.user_ode ? pmx::R_JIT_ODE_USER : pmx::R_JIT_ODE));
     if (model.custom && static_launcher() && r.mode == pmx::MODE_GRID && !c.ll) r.family = pmx::R_STATIC_AGRID;
@@ -455,9 +461,8 @@ int32_t jit_module(const pmx_model* model, const pmx_population* pop, const Devi
   auto it = modules.find(pop->device);
   if (it == modules.end()) {
     pmx::JitModule mod;
-    const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod,
-                                        d.eq_kind == PMX_EQ_ANALYTICAL ? pmx::JIT_ANALYTICAL
-                                                                       : (model->user_ode ? pmx::JIT_ODE_USER : pmx::JIT_ODE));
+    const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod, pmx::jit_kind(model->jit_spec),
+                                        model->jit_spec.checked);
     if (le != hipSuccess) return fail(PMX_ERR_HIP, std::string("loading the compiled model: ") + hipGetErrorString(le));
     it = modules.emplace(pop->device, mod).first;
   }
@@ -471,7 +476,8 @@ int32_t launch_jit(const pmx_model* model, const pmx_population* pop, const Devi
   const pmx::JitModule* jm = nullptr;
   const int32_t rc = jit_module(model, pop, ds, &jm);
   if (rc != PMX_OK) return rc;
-  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = r.solver != 0 ? 1 : 0;  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][ADAPT]
+  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][solver]; solver: 0 RK4, 1 adaptive, 2 checked RK4
+  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = r.solver == 3 ? 2 : (r.solver != 0 ? 1 : 0);
   int32_t s_chunk = r.s_chunk, n_ptiles = r.n_ptiles;
   if (r.family == pmx::R_STATIC_AGRID) {
     const int rc_s = static_launcher()(&a.m, &a.ops, a.theta, a.P, a.S, s_chunk, n_ptiles, a.pred, a.ld, a.status,

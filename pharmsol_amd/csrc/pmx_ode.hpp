@@ -66,6 +66,10 @@ __device__ __forceinline__ void rk4_step(const OdeLane<M>& L, double (&x)[M::NS]
   for (int i = 0; i < NS; ++i) x[i] = x[i] + (h / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
 }
 
+// Which stepper a walker is instantiated with (compile-time: a run-time switch between them costs the fixed-step
+// kernels their registers).
+enum : int { SOLV_RK4 = 0, SOLV_ADAPT = 1, SOLV_CHECKED = 2 };
+
 // ---- adaptive: Dormand-Prince 5(4) ("dopri5" / ode45), PMX_SOLVER_DOPRI5 --------------------------------------
 // One ATTEMPTED step of length h from (t, x): fills xn with the 5th-order solution and returns the scaled error
 // norm rms(e_i / (atol + rtol max(|x_i|, |xn_i|))); the step is acceptable iff the result is <= 1.
@@ -197,11 +201,41 @@ __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& 
   return sqrt(acc / static_cast<double>(NS));
 }
 
-// Step-size controller state of a lane: `h` = the controller's current proposal (carried from piece to piece).
+// Step-size controller state of a lane: `h` = the controller's current proposal (carried from piece to piece);
+// `failed`: step-size underflow (adaptive) / a probe found the step too coarse (checked RK4).
 struct AdaptState {
   double h;
   uint8_t failed;
 };
+
+// ---- checked RK4: the step-doubling probe, PMX_SOLVER_RK4_CHECKED -------------------------------------------------
+// The FIRST step of a piece, taken twice: xa = one step of length h (kept: a lane whose probes pass walks exactly what
+// plain RK4 walks), xb = two steps of h/2.  Richardson: e = 16/15 (xb - xa) estimates the h-step's local error; scaled
+// like dopri5_try's.  !(q <= 1) (NaN included) marks the lane failed for the rest of the subject: the step does not
+// resolve the model's rates, and fixed-step RK4 past its stability bound returns finite nonsense (ka = 150 /h at
+// h = 0.02: 7e27).  8 extra right-hand sides per piece, whatever its step count; the rates are constant over a piece,
+// so a linear body's first step is as hard as any later one.
+template <class M>
+__device__ __forceinline__ void rk4_probe_step(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
+                                               const double (&rs)[M::NR], double t, double h, AdaptState& as) {
+  constexpr int NS = M::NS;
+  double xb[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) xb[i] = x[i];
+  rk4_step<M>(L, x, rs, t, h);
+  rk4_step<M>(L, xb, rs, t, 0.5 * h);
+  rk4_step<M>(L, xb, rs, t + 0.5 * h, 0.5 * h);
+  double acc = 0.0;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const double e = (16.0 / 15.0) * (xb[i] - x[i]);
+    const double sc = m.ode_atol + m.ode_rtol * fmax(fabs(x[i]), fabs(xb[i]));
+    const double q = e / sc;
+    acc += q * q;
+  }
+  const double q = sqrt(acc / static_cast<double>(NS));
+  if (!(q <= 1.0)) as.failed = 1;  // (also NaN)
+}
 
 // One attempt inside the piece [.., t1]: tries min(h, t1 - t, h_max); on acceptance advances (t, x).  Returns true
 // while the piece is unfinished.  A step that underflows (h < 1e-13 max(1,|t|)) marks the lane failed and jumps to
@@ -356,12 +390,12 @@ __device__ __forceinline__ void ode_rates(const DevModel& m, const double* __res
 
 // One constant-rate piece [t0, t1] whose length is only known on the device (a lagged bolus split it):
 // n = ceil(dt / h_max) classic RK4 steps, the host compiler's rule (pmx_compile.cpp, ODE PROP ops).
-template <class M, bool ADAPT>
+template <class M, int SOLV>
 __device__ __forceinline__ void ode_piece(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
                                           const double (&rs)[M::NR], double t0, double t1, AdaptState& as) {
   const double dt = t1 - t0;
   if (!(dt > 0.0)) return;
-  if constexpr (ADAPT) {
+  if constexpr (SOLV == SOLV_ADAPT) {
     double t = t0;
     for (int32_t guard = 0; guard < 10000000 && dopri5_advance<M>(m, L, x, rs, t, t1, as); ++guard) {
     }
@@ -372,7 +406,12 @@ __device__ __forceinline__ void ode_piece(const DevModel& m, const OdeLane<M>& L
   if (nf > 1.0e7) nf = 1.0e7;  // a lane with an absurd lag must still terminate
   const int32_t n = static_cast<int32_t>(nf);
   const double h = dt / static_cast<double>(n);
-  for (int32_t k = 0; k < n; ++k) rk4_step<M>(L, x, rs, t0 + static_cast<double>(k) * h, h);
+  int32_t k = 0;
+  if constexpr (SOLV == SOLV_CHECKED) {
+    rk4_probe_step<M>(m, L, x, rs, t0, h, as);
+    k = 1;
+  }
+  for (; k < n; ++k) rk4_step<M>(L, x, rs, t0 + static_cast<double>(k) * h, h);
 }
 
 // A lagged bolus of slot `which` lands exactly on the time of the occasion's first remaining event (kind k_first): is it
@@ -393,7 +432,7 @@ __device__ __forceinline__ bool lag_lands_first(const LagState& ls, int which, u
 // without integration; every later event is reached by integrating from the clock if its time lies ahead.  Between an
 // early lagged bolus and the occasion's first remaining event no infusion can be active (infusions are events of the
 // occasion), so those pieces run with zero rates.  Returns the clock on arrival at the first remaining event.
-template <class M, bool ADAPT>
+template <class M, int SOLV>
 __device__ __forceinline__ double ode_lag_open_occasion(const DevModel& m, const DevOps& ops, LagState& ls, int64_t occ,
                                                         double t_first, uint32_t k_first, double t_rec, const OdeLane<M>& L,
                                                         const double* __restrict__ th, double (&x)[M::NS], AdaptState& as) {
@@ -417,7 +456,7 @@ __device__ __forceinline__ double ode_lag_open_occasion(const DevModel& m, const
     const double tau = lag_next(m, ops, ls, which);
     if (!(tau < t_first)) break;
     if (!first && tau > clk) {
-      ode_piece<M, ADAPT>(m, L, x, zero, clk, tau, as);
+      ode_piece<M, SOLV>(m, L, x, zero, clk, tau, as);
       clk = tau;
     }
     first = false;
@@ -432,13 +471,13 @@ __device__ __forceinline__ double ode_lag_open_occasion(const DevModel& m, const
     }
   }
   if (!first && t_first > clk && t_first < __longlong_as_double(0x7ff0000000000000LL)) {
-    ode_piece<M, ADAPT>(m, L, x, zero, clk, t_first, as);
+    ode_piece<M, SOLV>(m, L, x, zero, clk, t_first, as);
     clk = t_first;
   }
   return clk;
 }
 
-template <class M, bool ADAPT>
+template <class M, int SOLV>
 __device__ __forceinline__ void ode_lag_prop(const DevModel& m, const DevOps& ops, LagState& ls, double t0, double t1,
                                              const OdeLane<M>& L, const double (&rs)[M::NR],
                                              const double* __restrict__ th, double (&x)[M::NS], AdaptState& as) {
@@ -449,19 +488,20 @@ __device__ __forceinline__ void ode_lag_prop(const DevModel& m, const DevOps& op
     const double tau = lag_next(m, ops, ls, which);
     if (!(tau < t1)) break;
     if (tau > t) {
-      ode_piece<M, ADAPT>(m, L, x, rs, t, tau, as);
+      ode_piece<M, SOLV>(m, L, x, rs, t, tau, as);
       t = tau;
     }
     lag_apply_bolus<NS>(m, ops, ls, which, th, x);
   }
-  ode_piece<M, ADAPT>(m, L, x, rs, t, t1, as);
+  ode_piece<M, SOLV>(m, L, x, rs, t, t1, as);
 }
 
-template <class M, bool LAG, bool LL, bool ADAPT>
+template <class M, bool LAG, bool LL, int SOLV>
 __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& ops, const double* __restrict__ theta,
                                               int64_t P, int64_t S, int32_t s_chunk, int32_t n_ptiles,
                                               double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {
   constexpr int NS = M::NS;
+  constexpr bool ADAPT = SOLV == SOLV_ADAPT, CHECKED = SOLV == SOLV_CHECKED;
   const int64_t b = blockIdx.x;
   const int32_t ptile = static_cast<int32_t>(b % n_ptiles);
   const int64_t chunk = b / n_ptiles;
@@ -512,22 +552,29 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
         ode_rates<M>(m, ops.op_rate, o, ops.n_rate, rs);
         if constexpr (LAG) {
           const double t0 = uniformf64(as_const(ops.op_t0)[o]), t1 = uniformf64(as_const(ops.op_t1)[o]);
-          ode_lag_prop<M, ADAPT>(m, ops, ls, (clk > t0) ? clk : t0, t1, L, rs, th, x, as);
+          ode_lag_prop<M, SOLV>(m, ops, ls, (clk > t0) ? clk : t0, t1, L, rs, th, x, as);
           if (t1 > clk) clk = t1;
         } else if constexpr (ADAPT) {
-          ode_piece<M, true>(m, L, x, rs, uniformf64(as_const(ops.op_t0)[o]), uniformf64(as_const(ops.op_t1)[o]), as);
+          ode_piece<M, SOLV_ADAPT>(m, L, x, rs, uniformf64(as_const(ops.op_t0)[o]), uniformf64(as_const(ops.op_t1)[o]), as);
         } else {
           const double h = uniformf64(as_const(ops.op_b)[o]);
           const int32_t n = static_cast<int32_t>(uniform32(static_cast<uint32_t>(as_const(ops.op_n)[o])));
           double t0 = 0.0;  // only a custom (possibly non-autonomous) body reads the time
           if constexpr (M::CUSTOM) t0 = uniformf64(as_const(ops.op_t0)[o]);
-          for (int32_t k = 0; k < n; ++k) rk4_step<M>(L, x, rs, t0 + static_cast<double>(k) * h, h);
+          int32_t k = 0;
+          if constexpr (CHECKED) {
+            if (n > 0) {  // (wave-uniform)
+              rk4_probe_step<M>(m, L, x, rs, t0, h, as);
+              k = 1;
+            }
+          }
+          for (; k < n; ++k) rk4_step<M>(L, x, rs, t0 + static_cast<double>(k) * h, h);
         }
       } else if (kind == OP_OBS) {
         double y = ode_out<M>(m, L, x, io, a);
         if (LAG && st == PMX_PAIR_BAD_LAG) y = nanv;
-        if (ADAPT && as.failed) {  // step-size underflow somewhere before this row
-          if (st == PMX_PAIR_OK) st = PMX_PAIR_SOLVER_FAIL;
+        if ((ADAPT || CHECKED) && as.failed) {  // step-size underflow / a failed probe somewhere before this row
+          if (st == PMX_PAIR_OK) st = CHECKED ? PMX_PAIR_STEP_TOO_COARSE : PMX_PAIR_SOLVER_FAIL;
           y = nanv;
         }
         if constexpr (LL) {
@@ -547,7 +594,7 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
         L.occ = static_cast<int64_t>(a);
         ode_reset<M>(L, io, x);
         if constexpr (LAG)
-          clk = ode_lag_open_occasion<M, ADAPT>(m, ops, ls, static_cast<int64_t>(a), uniformf64(as_const(ops.op_t0)[o]),
+          clk = ode_lag_open_occasion<M, SOLV>(m, ops, ls, static_cast<int64_t>(a), uniformf64(as_const(ops.op_t0)[o]),
                                                 (meta >> 25) & 3u, uniformf64(as_const(ops.op_b)[o]), L, th, x, as);
       }
     }
@@ -563,11 +610,12 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
 // wave loop = a top-up of the rings when a lane ran dry, an op phase (idle lanes take up to two ops) and a stepping
 // phase (lanes inside a piece take up to ops.steps_per_trip steps), so lanes in different segments of different
 // subjects advance together (divergent timelines, C4) and none waits longer than a bounded number of steps.
-template <class M, bool LAG, bool LL, bool ADAPT>
+template <class M, bool LAG, bool LL, int SOLV>
 __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& ops, const double* __restrict__ theta,
                                               int64_t P, int64_t S, int32_t batch, double* __restrict__ pred,
                                               int64_t ld, uint8_t* __restrict__ status) {
   constexpr int NS = M::NS;
+  constexpr bool ADAPT = SOLV == SOLV_ADAPT, CHECKED = SOLV == SOLV_CHECKED;
   const int64_t n_pairs = batch ? S : S * P;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const bool lane_ok = i < n_pairs;
@@ -614,7 +662,8 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
   for (int k = 0; k < M::NR; ++k) rs[k] = 0.0;
   int32_t rem = 0;
   double h = 0.0;
-  // custom bodies may read the time: the open piece's start and step count (stage time = t_piece + k h)
+  // custom bodies may read the time: the open piece's start and step count (stage time = t_piece + k h); checked RK4
+  // knows a piece that has not taken a step yet by rem == n_piece
   double t_piece = 0.0;
   int32_t n_piece = 0;
   // adaptive solver: the running piece [t_run, t_run_end] and the lane's step-size proposal
@@ -743,16 +792,14 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
           } else {
             h = op_h;
             rem = op_steps;
-            if constexpr (M::CUSTOM) {
-              t_piece = op_t0;
-              n_piece = rem;
-            }
+            if constexpr (M::CUSTOM) t_piece = op_t0;
+            if constexpr (M::CUSTOM || CHECKED) n_piece = rem;
           }
         } else if (kind == OP_OBS) {
           double y = ode_out<M>(m, L, x, io, a);
           if (LAG && st == PMX_PAIR_BAD_LAG) y = nanv;
-          if (ADAPT && as.failed) {
-            if (st == PMX_PAIR_OK) st = PMX_PAIR_SOLVER_FAIL;
+          if ((ADAPT || CHECKED) && as.failed) {
+            if (st == PMX_PAIR_OK) st = CHECKED ? PMX_PAIR_STEP_TOO_COARSE : PMX_PAIR_SOLVER_FAIL;
             y = nanv;
           }
           if constexpr (LL) {
@@ -813,7 +860,18 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
         for (int32_t j = 0; j < spt && stepping; ++j) stepping = dopri5_advance<M>(m, L, x, rs, t_run, t_run_end, as);
       } else {
         const int32_t kk = rem < spt ? rem : spt;
-        for (int32_t j = 0; j < kk; ++j) {
+        int32_t j = 0;
+        if constexpr (CHECKED) {
+          // The probe is the first step of the piece a lane opened in the op phase above.  It is taken HERE, at the
+          // head of the stepping phase, where every lane of the wave that opened a piece in either action of this trip
+          // probes together; inside the op phase's action loop two lanes opening pieces in different actions would
+          // each make the rest of the wave wait for three steps.
+          if (rem == n_piece) {
+            rk4_probe_step<M>(m, L, x, rs, M::CUSTOM ? t_piece : 0.0, h, as);
+            j = 1;
+          }
+        }
+        for (; j < kk; ++j) {
           double t = 0.0;
           if constexpr (M::CUSTOM) t = t_piece + static_cast<double>(n_piece - rem + j) * h;
           rk4_step<M>(L, x, rs, t, h);

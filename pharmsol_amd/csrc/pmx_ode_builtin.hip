@@ -95,38 +95,39 @@ struct OdeModel<PMX_ODE_ONE_CMT_MM> {  // p=[vmax,km,v]
 };
 
 
-template <int MODEL, bool LAG, bool LL, bool ADAPT>
+template <int MODEL, bool LAG, bool LL, int SOLV>
 __global__ __launch_bounds__(kBlock) void pmx_ode_rk4_grid(DevModel m, DevOps ops, const double* __restrict__ theta,
                                                            int64_t P, int64_t S, int32_t s_chunk, int32_t n_ptiles,
                                                            double* __restrict__ pred, int64_t ld,
                                                            uint8_t* __restrict__ status) {
-  ode_grid_body<OdeModel<MODEL>, LAG, LL, ADAPT>(m, ops, theta, P, S, s_chunk, n_ptiles, pred, ld, status);
+  ode_grid_body<OdeModel<MODEL>, LAG, LL, SOLV>(m, ops, theta, P, S, s_chunk, n_ptiles, pred, ld, status);
 }
 
-template <int MODEL, bool LAG, bool LL, bool ADAPT>
+template <int MODEL, bool LAG, bool LL, int SOLV>
 __global__ __launch_bounds__(kBlock) void pmx_ode_rk4_pair(DevModel m, DevOps ops, const double* __restrict__ theta,
                                                            int64_t P, int64_t S, int32_t batch,
                                                            double* __restrict__ pred, int64_t ld,
                                                            uint8_t* __restrict__ status) {
-  ode_pair_body<OdeModel<MODEL>, LAG, LL, ADAPT>(m, ops, theta, P, S, batch, pred, ld, status);
+  ode_pair_body<OdeModel<MODEL>, LAG, LL, SOLV>(m, ops, theta, P, S, batch, pred, ld, status);
 }
 
 
 template <int MODEL>
 hipError_t launch_ode_m(const LaunchArgs& a, const Route& r) {
   // (the same instantiation serves both adaptive steppers: DevModel::ode_stiff)
-  return dispatch([&](auto lag, auto ll, auto adapt, auto pair) {
-    constexpr bool LAG = decltype(lag)::value, LL = decltype(ll)::value, ADAPT = decltype(adapt)::value;
+  return dispatch([&](auto lag, auto ll, auto adapt, auto checked, auto pair) {
+    constexpr bool LAG = decltype(lag)::value, LL = decltype(ll)::value;
+    constexpr int SOLV = decltype(checked)::value ? SOLV_CHECKED : (decltype(adapt)::value ? SOLV_ADAPT : SOLV_RK4);
     hipStream_t st = static_cast<hipStream_t>(a.stream);
     const dim3 grid(static_cast<uint32_t>(r.blocks)), block(r.threads);
     if constexpr (!decltype(pair)::value)
-      hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, ADAPT>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, r.s_chunk,
+      hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, r.s_chunk,
                          r.n_ptiles, a.pred, a.ld, a.status);
     else
-      hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, ADAPT>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred,
+      hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred,
                          a.ld, a.status);
     return hipGetLastError();
-  }, r.lag, r.ll, r.solver != 0, r.mode != MODE_GRID);
+  }, r.lag, r.ll, r.solver == 1 || r.solver == 2, r.solver == 3, r.mode != MODE_GRID);
 }
 
 }  // namespace

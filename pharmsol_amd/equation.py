@@ -550,14 +550,18 @@ class ODE(Equation):
         """``ODE::with_solver`` (ode/mod.rs:134-150).  The reference's diffsol solvers are replaced: ``"rk4"`` = fixed
         step (default), ``"dopri5"`` = adaptive Dormand-Prince 5(4) with per-lane step control (the role of
         ``ExplicitRk(Tsit45)``), ``"ros2"`` (alias ``"stiff"``) = the L-stable Rosenbrock method ROS2 with the same step
-        control, for stiff systems (the role of ``Bdf`` / ``Sdirk``, ode/mod.rs:60-77)."""
+        control, for stiff systems (the role of ``Bdf`` / ``Sdirk``, ode/mod.rs:60-77).  ``"rk4-checked"`` = the
+        fixed-step walk of ``"rk4"`` with a step-doubling probe at the head of every integration piece: a support point
+        whose rates ``h_max`` does not resolve (Richardson estimate of the first step's error beyond ``with_tolerances``)
+        comes back NaN from that piece on, with pair status ``PMX_PAIR_STEP_TOO_COARSE``, instead of finite nonsense;
+        every other pair gets plain RK4's numbers."""
         self.ode_solver = {"rk4": _abi.PMX_SOLVER_RK4, "dopri5": _abi.PMX_SOLVER_DOPRI5, "ros2": _abi.PMX_SOLVER_ROS2,
-                           "stiff": _abi.PMX_SOLVER_ROS2}[solver]
+                           "stiff": _abi.PMX_SOLVER_ROS2, "rk4-checked": _abi.PMX_SOLVER_RK4_CHECKED}[solver]
         self._handle = None
         return self
 
     def with_tolerances(self, rtol: float, atol: float) -> "ODE":
-        """``ODE::with_tolerances`` (ode/mod.rs:152-166); read by the adaptive solver."""
+        """``ODE::with_tolerances`` (ode/mod.rs:152-166); read by the adaptive solvers and by ``"rk4-checked"``'s probe."""
         self.ode_rtol, self.ode_atol = float(rtol), float(atol)
         self._handle = None
         return self

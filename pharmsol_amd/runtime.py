@@ -230,6 +230,18 @@ def _as_model(model) -> DeviceModel:
     return dm
 
 
+def _check_host(rc: int, status: np.ndarray, dm, raise_on_pair_failure: bool) -> None:
+    """``_ffi.check`` of a host-pointer call; a raised pair failure says what a ``"rk4-checked"`` model found."""
+    if rc == _abi.PMX_ERR_PAIR_FAILED and raise_on_pair_failure:
+        n = int((status == _abi.PMX_PAIR_STEP_TOO_COARSE).sum())
+        if n > 0:
+            raise _abi.PmxError(rc, f"{n} (subject, support point) pair(s) have status PMX_PAIR_STEP_TOO_COARSE: the RK4 step "
+                                    f"h_max = {dm.desc.rk4_h_max:g} does not resolve their rates (checked at the head of every "
+                                    "integration piece); shorten it with with_step(...), or integrate with "
+                                    "with_solver('dopri5') or with_solver('ros2')")
+    _ffi.check(rc, allow_pair_failures=not raise_on_pair_failure)
+
+
 def predict_host(model, flat: FlatPopulation, theta: np.ndarray, device: int = 0, batch: bool = False,
                  raise_on_pair_failure: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """Host-pointer ABI form (``pmx_predict`` / ``pmx_predict_batch``): numpy in, numpy out."""
@@ -252,7 +264,7 @@ def predict_host(model, flat: FlatPopulation, theta: np.ndarray, device: int = 0
         pred = np.full((pop.n_observations, P), np.nan)
         status = np.zeros((pop.n_subjects, P), dtype=np.uint8)
         rc = L.pmx_predict(dm.handle, pop.handle, theta.ctypes.data, P, pred.ctypes.data, P, status.ctypes.data)
-    _ffi.check(rc, allow_pair_failures=not raise_on_pair_failure)
+    _check_host(rc, status, dm, raise_on_pair_failure)
     return pred, status
 
 
@@ -306,7 +318,7 @@ def loglik_host(model, flat: FlatPopulation, error_models, theta: np.ndarray, de
     status = np.zeros((pop.n_subjects, P), dtype=np.uint8)
     rc = L.pmx_loglik(dm.handle, pop.handle, C.cast(em, C.c_void_p), theta.ctypes.data, P, ll.ctypes.data, P,
                       status.ctypes.data)
-    _ffi.check(rc, allow_pair_failures=not raise_on_pair_failure)
+    _check_host(rc, status, dm, raise_on_pair_failure)
     return ll, status
 
 
