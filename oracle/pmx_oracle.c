@@ -812,8 +812,25 @@ static void ode_f(const ctx_t* c, double t, const double* x, const double* p, co
   }
 }
 
-/* One constant-rate piece [t0, t1] with n = ceil((t1-t0)/h_max) classic RK4 steps. */
-static void rk4_piece(const ctx_t* c, double* x, const double* p, const double* rate, double t0, double t1) {
+/* One classic RK4 step from (t, x) to xn (xn may alias x). */
+static void rk4_step(const ctx_t* c, const double* x, const double* p, const double* rate, double t, double h, double* xn) {
+  int ns = c->m->nstates;
+  double k1[PMX_MAX_STATES], k2[PMX_MAX_STATES], k3[PMX_MAX_STATES], k4[PMX_MAX_STATES], xt[PMX_MAX_STATES];
+  ode_f(c, t, x, p, rate, k1); /* stage times t, t + h/2, t + h/2, t + h */
+  for (int i = 0; i < ns; i++) xt[i] = x[i] + (0.5 * h) * k1[i];
+  ode_f(c, t + 0.5 * h, xt, p, rate, k2);
+  for (int i = 0; i < ns; i++) xt[i] = x[i] + (0.5 * h) * k2[i];
+  ode_f(c, t + 0.5 * h, xt, p, rate, k3);
+  for (int i = 0; i < ns; i++) xt[i] = x[i] + h * k3[i];
+  ode_f(c, t + h, xt, p, rate, k4);
+  for (int i = 0; i < ns; i++) xn[i] = x[i] + (h / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
+}
+
+/* One constant-rate piece [t0, t1] with n = ceil((t1-t0)/h_max) classic RK4 steps.  PMX_SOLVER_RK4_CHECKED (`coarse`
+ * not NULL): the first step is also taken as two half steps; Richardson's estimate e = 16/15 (xb - xa) of its local
+ * error, q = rms(e_i / (atol + rtol max(|xa_i|, |xb_i|))), must be <= 1 (a NaN fails) or *coarse is set.  The full
+ * step xa is kept either way, so a pair whose probes pass walks what plain RK4 walks. */
+static void rk4_piece(const ctx_t* c, double* x, const double* p, const double* rate, double t0, double t1, int* coarse) {
   const pmx_model_desc* m = c->m;
   double dt = t1 - t0;
   if (!(dt > 0.0)) return;
@@ -822,18 +839,18 @@ static void rk4_piece(const ctx_t* c, double* x, const double* p, const double* 
   int64_t n = (int64_t)nf;
   double h = dt / (double)n;
   int ns = m->nstates;
-  double k1[PMX_MAX_STATES], k2[PMX_MAX_STATES], k3[PMX_MAX_STATES], k4[PMX_MAX_STATES], xt[PMX_MAX_STATES];
-  for (int64_t s = 0; s < n; s++) {
-    double t = t0 + (double)s * h; /* stage times t, t + h/2, t + h/2, t + h */
-    ode_f(c, t, x, p, rate, k1);
-    for (int i = 0; i < ns; i++) xt[i] = x[i] + (0.5 * h) * k1[i];
-    ode_f(c, t + 0.5 * h, xt, p, rate, k2);
-    for (int i = 0; i < ns; i++) xt[i] = x[i] + (0.5 * h) * k2[i];
-    ode_f(c, t + 0.5 * h, xt, p, rate, k3);
-    for (int i = 0; i < ns; i++) xt[i] = x[i] + h * k3[i];
-    ode_f(c, t + h, xt, p, rate, k4);
-    for (int i = 0; i < ns; i++) x[i] = x[i] + (h / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
+  if (coarse && !*coarse) {
+    double xa[PMX_MAX_STATES], xb[PMX_MAX_STATES], sum = 0.0;
+    rk4_step(c, x, p, rate, t0, h, xa);
+    rk4_step(c, x, p, rate, t0, 0.5 * h, xb);
+    rk4_step(c, xb, p, rate, t0 + 0.5 * h, 0.5 * h, xb);
+    for (int i = 0; i < ns; i++) {
+      double e = (16.0 / 15.0) * (xb[i] - xa[i]) / (m->ode_atol + m->ode_rtol * fmax(fabs(xa[i]), fabs(xb[i])));
+      sum += e * e;
+    }
+    if (!(sqrt(sum / (double)ns) <= 1.0)) *coarse = 1;
   }
+  for (int64_t s = 0; s < n; s++) rk4_step(c, x, p, rate, t0 + (double)s * h, h, x);
 }
 
 /* ---- PMX_SOLVER_DOPRI5: Dormand-Prince 5(4) with step-size control (the build's stand-in for the reference's
@@ -995,6 +1012,7 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
   int64_t row = 0; /* prediction row within the subject */
   uint8_t st = PMX_PAIR_OK;
   adapt_t adapt = {m->rk4_h_max, 0}; /* adaptive solver: the proposal restarts with every subject */
+  int coarse = 0;                    /* checked RK4: some piece's probe has failed */
   ctx_t ctx;
   ctx.m = m;
   ctx.theta = theta;
@@ -1170,6 +1188,10 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
             if (st == PMX_PAIR_OK) st = PMX_PAIR_SOLVER_FAIL;
             pr = NAN;
           }
+          if (coarse) { /* a failed step-doubling probe before this row */
+            if (st == PMX_PAIR_OK) st = PMX_PAIR_STEP_TOO_COARSE;
+            pr = NAN;
+          }
           if (st == PMX_PAIR_OK && !isfinite(pr)) st = PMX_PAIR_NONFINITE;
           pred[row * pred_stride] = pr;
           row++;
@@ -1188,10 +1210,10 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
               double s = sc->inf[k].time, en = s + sc->inf[k].duration;
               if (s <= t && t < en) rate[sc->inf[k].input] += sc->inf[k].amount / sc->inf[k].duration;
             }
-            if (m->ode_solver != PMX_SOLVER_RK4)
-              dopri5_piece(&ctx, x, theta, rate, t, stop, &adapt);
+            if (m->ode_solver == PMX_SOLVER_RK4 || m->ode_solver == PMX_SOLVER_RK4_CHECKED)
+              rk4_piece(&ctx, x, theta, rate, t, stop, m->ode_solver == PMX_SOLVER_RK4_CHECKED ? &coarse : 0);
             else
-              rk4_piece(&ctx, x, theta, rate, t, stop);
+              dopri5_piece(&ctx, x, theta, rate, t, stop, &adapt);
             t = stop;
           }
         }

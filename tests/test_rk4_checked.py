@@ -2,8 +2,8 @@
 every integration piece the step is also taken as two half steps; Richardson's estimate of its local error, in the
 adaptive solvers' scaled norm, must be <= 1 or the pair ends as PMX_PAIR_STEP_TOO_COARSE with NaN rows from that piece on.
 
-The expectation is a plain numpy restatement of the probe and of the RK4 march (no oracle: its dispatch treats every
-non-RK4 solver as adaptive).  Only cases whose numpy q is <= 0.1 or >= 10 on every deciding piece are used, so an FMA
+The expectation is a plain numpy restatement of the probe and of the RK4 march (independent of the oracle's twin of the
+rule, which tests/test_oracle_ode_exact.py holds to exact arithmetic).  Only cases whose numpy q is <= 0.1 or >= 10 on every deciding piece are used, so an FMA
 contraction on the device cannot flip a verdict; the band 15 <= ka <= 25, where q crosses 1, is left out.
 
 Tolerances: a lane whose probes pass keeps the full step, i.e. it walks what plain RK4 walks - 1e-12 relative between the
