@@ -9,12 +9,15 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
 # the kernel units: one translation unit per kernel family (pmx_lanes.hpp lists them)
 KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util
-OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
+OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 
 all: $(LIB) oracle
 
-$(CSRC)/build/pmx_compile.o: $(CSRC)/pmx_compile.cpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_devtypes.hpp include/pmx.h
+# the population compiler: pure host code (pmx_compile.cpp: population and op stream; pmx_plan.cpp: class plan, records)
+PLANSRC := $(CSRC)/pmx_compile.cpp $(CSRC)/pmx_plan.cpp
+PLANHDR := $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_devtypes.hpp include/pmx.h
+$(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o: $(CSRC)/build/%.o: $(CSRC)/%.cpp $(PLANHDR)
 	@mkdir -p $(CSRC)/build
 	g++ $(HOSTFLAGS) -c $< -o $@
 
@@ -62,7 +65,18 @@ oracle:
 clean:
 	rm -rf $(CSRC)/build pharmsol_amd/lib oracle/_build
 
-.PHONY: all oracle clean asm
+.PHONY: all oracle clean asm plan_fingerprint plan_fingerprint_san
+
+# Fingerprint of every array the population compiler produces (tests/test_plan_fingerprint.py compares its output with
+# tests/golden/plan_fingerprints.txt).  Host sources only.  FPBIN: where the program goes.  plan_fingerprint_san: the same
+# program under AddressSanitizer + UBSan, run stand-alone: `make plan_fingerprint_san && tests/cpp/plan_fingerprint_san`
+FPBIN ?= tests/cpp/plan_fingerprint
+plan_fingerprint: $(FPBIN)
+$(FPBIN): tests/cpp/plan_fingerprint.cpp $(PLANSRC) $(PLANHDR)
+	g++ $(HOSTFLAGS) -I$(CSRC) -o $@ tests/cpp/plan_fingerprint.cpp $(PLANSRC)
+plan_fingerprint_san: tests/cpp/plan_fingerprint_san
+tests/cpp/plan_fingerprint_san: tests/cpp/plan_fingerprint.cpp $(PLANSRC) $(PLANHDR)
+	g++ $(HOSTFLAGS) -I$(CSRC) -fsanitize=address,undefined -fno-omit-frame-pointer -o $@ tests/cpp/plan_fingerprint.cpp $(PLANSRC)
 
 # C++ host-facade test binary (links the product library and, as the checker, the CPU oracle)
 tests/cpp/facade_test: tests/cpp/facade_test.cpp include/pharmsol_hip.hpp include/pmx.h $(LIB) oracle

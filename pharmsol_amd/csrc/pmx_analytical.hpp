@@ -181,8 +181,8 @@ __device__ __forceinline__ void user_walk_subject(const DevOps& ops, const doubl
 #pragma unroll 1
   for (int64_t o = o0; o < o1; ++o) {
     const uint32_t meta = u32(as_const(ops.op_meta)[o]);
-    const uint32_t kind = meta & 0xffu;
-    const int io = static_cast<int>((meta >> 8) & 0xffffu);
+    const uint32_t kind = meta & kOpKindMask;
+    const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
     const double a = uf(as_const(ops.op_a)[o]);
     if (kind == OP_PROP) {
       double rate[M::NIN];
@@ -195,7 +195,7 @@ __device__ __forceinline__ void user_walk_subject(const DevOps& ops, const doubl
         for (int i = 0; i < M::NIN; ++i) rate[i] = (i < ops.n_rate) ? uf(as_const(ops.op_rate)[o * ops.n_rate + i]) : 0.0;
       }
       const double t0 = uf(as_const(ops.op_t0)[o]), t1 = uf(as_const(ops.op_t1)[o]);
-      if (((meta >> 24) & 1u) == 0u) s.fresh = true;  // first sub-segment of a solve
+      if (((meta >> kOpContinuesShift) & 1u) == 0u) s.fresh = true;  // first sub-segment of a solve
       double t = t0;
       if constexpr (M::HAS_LAG) {
 #pragma unroll 1

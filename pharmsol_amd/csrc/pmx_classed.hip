@@ -273,8 +273,8 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
           }
         }
       }
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       if (kind == OP_PROP) {
         if constexpr (LAGC) {
           // lag_prop: split [t0, t1) at this lane's lagged landing times
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
             if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
           }
         } else {
-          const uint32_t rung = (meta >> 27) & 7u;
+          const uint32_t rung = (meta >> kOpRungShift) & kOpRungMask;
           if (rung == 0u) {
             LM::S::exps(coef, kUpfront ? up_dt : prog_dt[o], ex);
           } else if (rung != 1u) {
@@ -375,18 +375,18 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
           if (started && t_first > t && t_first < kInf) advance_all(t_first - t, voff, false);
         }
       }  // (kind == OP_OBS: a second observation at the same instant, no state change)
-      if ((meta >> 24) & 1u) {  // the observation fused into this step (pmx_compile.cpp build_class_plan)
+      if ((meta >> kOpObsAfterShift) & 1u) {  // the observation fused into this step (pmx_plan.cpp build_class_plan)
         if constexpr (LAGC) {
           // no PROP step in front of this observation (bit 31; its time sits in the step's t1 slot): the lagged boluses
           // landing before it come first, without propagation (the members share the landing times)
-          if (meta >> 31) {
+          if (meta >> kOpFlushShift) {
             const double t_obs = as_const(cp.prog_t1)[o];
             while (lag_tau() < t_obs) bolus_all();
           }
         }
-        const int oq = static_cast<int>((meta >> 25) & 3u);
+        const int oq = static_cast<int>((meta >> kOpOutShift) & kOpOutMask);
         // (pm_ models: the plan only holds subjects that never dose the pad slot and models that never read it, so
-        // kernel state = model state - 1 is all the wrapper amounts to; pmx_compile.cpp build_class_plan)
+        // kernel state = model state - 1 is all the wrapper amounts to; pmx_plan.cpp build_class_plan)
         int out_state = m.out[0].state - m.pm;
         double inv_vol = inv_vol0;
         if (oq != 0) {  // outputs beyond the first: rare, re-derive the volume instead of keeping 4 live

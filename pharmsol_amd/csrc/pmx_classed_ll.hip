@@ -190,7 +190,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? PMX_LL_WAVES : 
               ov_y[j] = __longlong_as_double(static_cast<int64_t>((static_cast<uint64_t>(yc[2 * j + 1]) << 32) | yc[2 * j]));
               ov_w[j] = __longlong_as_double(static_cast<int64_t>((static_cast<uint64_t>(wc[2 * j + 1]) << 32) | wc[2 * j]));
             }
-            const uint32_t rung = (static_cast<uint32_t>(w) >> 27) & 7u;  // 1..4
+            const uint32_t rung = (static_cast<uint32_t>(w) >> kOpRungShift) & kOpRungMask;  // 1..4
             if (rung != 1u) {
 #pragma unroll
               for (int e = 0; e < LM::S::NE; ++e) {
@@ -238,11 +238,11 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? PMX_LL_WAVES : 
       const auto rp = as_const(reinterpret_cast<const uint64_t*>(recs)) + 2 * k;
       const uint64_t w = rp[0], dtb = rp[1];
       const uint32_t meta = static_cast<uint32_t>(w);
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       const bool has_val = ((rate_mask >> (k < 63 ? k : 63)) & 1ull) != 0ull;
       if (kind == OP_PROP) {
-        const uint32_t rung = (meta >> 27) & 7u;
+        const uint32_t rung = (meta >> kOpRungShift) & kOpRungMask;
         if (rung == 0u) {
           LM::S::exps(coef, __longlong_as_double(static_cast<int64_t>(dtb)), ex);
         } else if (rung != 1u) {
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? PMX_LL_WAVES : 
           for (int j = 0; j < G; ++j) x[j][i] = xi;
         }
       }
-      if ((meta >> 24) & 1u) {  // the observation fused into this step
+      if ((meta >> kOpObsAfterShift) & 1u) {  // the observation fused into this step
         const auto ov = cobs + cobs_off;
         double ov_y[G], ov_w[G];
 #pragma unroll
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? PMX_LL_WAVES : 
           ov_y[j] = ov[j];
           ov_w[j] = ov[G + j];
         }
-        const int oq = static_cast<int>((meta >> 25) & 3u);
+        const int oq = static_cast<int>((meta >> kOpOutShift) & kOpOutMask);
         int out_state = out_state0;
         double inv_vol = inv_vol0;
         if (oq != 0) {  // outputs beyond the first: rare (see pmx_analytical_classed for why it is written this way)

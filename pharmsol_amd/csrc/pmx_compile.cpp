@@ -183,49 +183,94 @@ int32_t build_host_population(const pmx_population_desc* d, HostPopulation* hp, 
   return PMX_OK;
 }
 
-int32_t compile_ops(const HostPopulation& hp, const CompileKey& key, OpStream* os, std::string* err) {
-  const int32_t nc = hp.n_cov;
-  const bool ode = key.eq_kind == PMX_EQ_ODE;
-  const int32_t n_rate = key.n_rate;
-  os->key = key;
-  os->subj_op_off.assign(hp.n_subjects + 1, 0);
-  os->op_meta.clear();
-  os->op_a.clear();
-  os->op_b.clear();
-  os->op_n.clear();
-  os->op_rate.clear();
-  os->op_cov.clear();
-  os->op_fac.clear();
-  os->op_t0.clear();
-  os->op_t1.clear();
-  os->lagb_off.clear();
-  os->lagb_time.clear();
-  os->lagb_amount.clear();
-  os->lagb_input.clear();
-  os->max_lagb_per_list = 0;
-  os->prop_cache_used = 0;
-  os->n_prop_reused = 0;
-  os->n_prop = 0;
-  const uint32_t lag_mask = key.lag_mask;
+// ------------------------------------------------------------------------------------
+// op stream
+// ------------------------------------------------------------------------------------
+namespace {
+
+// Lagged boluses leave the event list (the device merges them at t + lag(theta)); what remains is walked exactly like
+// before.  Slot k = the k-th lagged input, or the one list all inputs of a lag_merge key share.
+struct LagLists {
   int32_t slot_of_input[PMX_MAX_INPUTS];
   int32_t n_slots = 0;
-  for (int i = 0; i < PMX_MAX_INPUTS; ++i) slot_of_input[i] = ((lag_mask >> i) & 1u) ? (key.lag_merge ? 0 : n_slots++) : -1;
-  if (key.lag_merge && lag_mask != 0) n_slots = 1;
-  os->n_lag_slots = n_slots;
-  struct LagBolus {
-    double first, second;  // recorded time, amount
-    int32_t input;
-  };
-  std::vector<std::vector<LagBolus>> lagb(n_slots > 0 ? n_slots : 1);  // per slot, this occasion
-  if (n_slots > 0) os->lagb_off.push_back(0);
-  const bool times = n_slots > 0 || key.want_times;  // PROP ops carry their absolute [t0, t1)
 
-  std::vector<double> covv(nc > 0 ? nc : 1, 0.0);
-  std::vector<double> rate(n_rate > 0 ? n_rate : 1, 0.0);
+  explicit LagLists(const CompileKey& key) {
+    for (int i = 0; i < PMX_MAX_INPUTS; ++i)
+      slot_of_input[i] = ((key.lag_mask >> i) & 1u) ? (key.lag_merge ? 0 : n_slots++) : -1;
+    if (key.lag_merge && key.lag_mask != 0) n_slots = 1;
+  }
+  bool is_lagged(const HostPopulation& hp, int64_t e) const {
+    return n_slots > 0 && hp.ev_kind[e] == PMX_EV_BOLUS && hp.ev_io[e] < PMX_MAX_INPUTS && slot_of_input[hp.ev_io[e]] >= 0;
+  }
+  int64_t next_kept(const HostPopulation& hp, int64_t e, int64_t e1) const {  // first event of [e, e1) that stays in the list
+    while (e < e1 && is_lagged(hp, e)) ++e;
+    return e;
+  }
+  // Lists the lagged boluses of occasion [e0, e1) per slot, in event order, and notes on the occasion's RESET op what a
+  // lane needs to know of the remaining list: op_t0 = the time of its first event (+inf: none) and, in First, its kind.
+  // ODE: which event is FIRST in the re-sorted list decides what is applied at the solver clock without integration
+  // (pmx_ode.hpp "the solver clock"); at equal times a bolus sorts behind an observation and in front of an infusion
+  // (event.rs:292-304).
+  void extract(const HostPopulation& hp, int64_t e0, int64_t e1, size_t reset_op, OpStream* os) const {
+    const int64_t first = next_kept(hp, e0, e1);
+    os->op_t0[reset_op] = first < e1 ? hp.ev_time[first] : std::numeric_limits<double>::infinity();
+    os->op_meta[reset_op] |= (first < e1 ? static_cast<uint32_t>(hp.ev_kind[first]) : 3u) << kOpFirstShift;
+    for (int32_t k = 0; k < n_slots; ++k) {
+      const int64_t before = static_cast<int64_t>(os->lagb_time.size());
+      for (int64_t e = e0; e < e1; ++e) {
+        if (!is_lagged(hp, e) || slot_of_input[hp.ev_io[e]] != k) continue;
+        os->max_input_used = std::max<int32_t>(os->max_input_used, hp.ev_io[e]);
+        os->lagb_time.push_back(hp.ev_time[e]);
+        os->lagb_amount.push_back(hp.ev_value[e]);
+        os->lagb_input.push_back(hp.ev_io[e]);
+      }
+      os->lagb_off.push_back(static_cast<int64_t>(os->lagb_time.size()));
+      os->max_lagb_per_list = std::max(os->max_lagb_per_list, os->lagb_off.back() - before);
+    }
+  }
+};
+
+// Appends ops: one method per kind, each filling every column the stream carries for this key.
+struct OpWriter {
+  const HostPopulation& hp;
+  const CompileKey& key;
+  OpStream* os;
+  const bool ode, times;  // times: ops carry absolute [t0, t1) (PROP) / the first event's time (RESET)
+  std::vector<double> covv;
   bool cov_missing = false;
 
-  auto push = [&](uint32_t kind, uint32_t io, double a, double b, int32_t n, const double* rates, int64_t occ,
-                  double t_cov, bool want_cov) {
+  OpWriter(const HostPopulation& hp_, const CompileKey& key_, OpStream* os_, bool times_)
+      : hp(hp_), key(key_), os(os_), ode(key_.eq_kind == PMX_EQ_ODE), times(times_), covv(hp_.n_cov > 0 ? hp_.n_cov : 1, 0.0) {}
+
+  // initial_state: zeros, init only for occasion index 0 (analytical/mod.rs:409-426); op_a = the global occasion index
+  size_t reset(int64_t occ) {
+    put(OP_RESET, hp.occ_index[occ] == 0 ? 1u : 0u, static_cast<double>(occ), 0.0, 0, nullptr);
+    no_covariates();
+    return os->op_meta.size() - 1;
+  }
+  void bolus(int64_t e) {  // (op_b: its time, for a user fa / bolus jump)
+    os->max_input_used = std::max<int32_t>(os->max_input_used, hp.ev_io[e]);
+    put(OP_BOLUS, hp.ev_io[e], hp.ev_value[e], hp.ev_time[e], 0, nullptr);
+    no_covariates();
+  }
+  void obs(int64_t occ, int64_t e) {
+    put(OP_OBS, hp.ev_io[e], hp.ev_time[e], 0.0, 0, nullptr);
+    covariates_at(occ, hp.ev_time[e]);
+  }
+  // one constant-rate piece [t0, t1): b = rateiv[0] (analytical) / the RK4 step (ODE, n of them); `rates`: every input's
+  // rate (ODE and full_rates streams); covariates are evaluated at t_cov
+  void prop(int64_t occ, double t0, double t1, double b, int32_t n, const double* rates, double t_cov) {
+    put(OP_PROP, 0, t1 - t0, b, n, rates);
+    covariates_at(occ, t_cov);
+    if (times) {
+      os->op_t0.back() = t0;
+      os->op_t1.back() = t1;
+    }
+    os->n_prop++;
+  }
+
+ private:
+  void put(uint32_t kind, uint32_t io, double a, double b, int32_t n, const double* rates) {
     os->op_meta.push_back(make_meta(kind, io));
     os->op_a.push_back(a);
     os->op_b.push_back(b);
@@ -235,802 +280,300 @@ int32_t compile_ops(const HostPopulation& hp, const CompileKey& key, OpStream* o
     }
     if (ode) os->op_n.push_back(n);
     if (ode || key.full_rates)
-      for (int32_t r = 0; r < n_rate; ++r) os->op_rate.push_back(rates ? rates[r] : 0.0);
-    if (nc > 0 && !key.user_cov) {
-      for (int32_t c = 0; c < nc; ++c) {
-        double v = 0.0;
-        if (want_cov && !hp.interpolate(occ, c, t_cov, &v)) cov_missing = true;
-        os->op_cov.push_back(v);
-        covv[c] = v;
-      }
-      // the factors of every derived value at these covariates (expand/analytical.rs:254,286; bindings.rs:98-117),
-      // written exactly like the per-lane expression they replace
-      for (int32_t d = 0; d < key.n_derived; ++d)
-        for (int32_t k = 0; k < PMX_MAX_FACTORS; ++k) {
-          double fac = 1.0;
-          if (want_cov && k < key.derived[d].n_factors) {
-            const pmx_factor& f = key.derived[d].f[k];
-            const double cv = covv[f.cov];
-            fac = (f.op == PMX_F_POW) ? std::pow(cv / f.ref, f.coef) : (1.0 + f.coef * (cv - f.ref));
-          }
-          os->op_fac.push_back(fac);
-        }
+      for (int32_t r = 0; r < key.n_rate; ++r) os->op_rate.push_back(rates ? rates[r] : 0.0);
+  }
+  void no_covariates() {  // RESET, BOLUS: zero covariates, unit factors
+    if (hp.n_cov == 0 || key.user_cov) return;
+    os->op_cov.insert(os->op_cov.end(), static_cast<size_t>(hp.n_cov), 0.0);
+    os->op_fac.insert(os->op_fac.end(), static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS, 1.0);
+  }
+  // the covariates an OBS / PROP sees and the factors of every derived value at them (expand/analytical.rs:254,286;
+  // bindings.rs:98-117), written exactly like the per-lane expression they replace
+  void covariates_at(int64_t occ, double t) {
+    if (hp.n_cov == 0 || key.user_cov) return;
+    for (int32_t c = 0; c < hp.n_cov; ++c) {
+      double v = 0.0;
+      if (!hp.interpolate(occ, c, t, &v)) cov_missing = true;
+      os->op_cov.push_back(v);
+      covv[c] = v;
     }
-  };
+    for (int32_t d = 0; d < key.n_derived; ++d)
+      for (int32_t k = 0; k < PMX_MAX_FACTORS; ++k) {
+        double fac = 1.0;
+        if (k < key.derived[d].n_factors) {
+          const pmx_factor& f = key.derived[d].f[k];
+          const double cv = covv[f.cov];
+          fac = (f.op == PMX_F_POW) ? std::pow(cv / f.ref, f.coef) : (1.0 + f.coef * (cv - f.ref));
+        }
+        os->op_fac.push_back(fac);
+      }
+  }
+};
 
+// The occasion walks: the events of one occasion -> ops.
+struct OccasionWalker {
+  const HostPopulation& hp;
+  const CompileKey& key;
+  OpStream* os;
+  LagLists lag;
+  OpWriter w;
   std::vector<ActiveInfusion> inf;
-  std::vector<double> ts, bounds;
-  int32_t max_input_used = -1;
+  std::vector<double> ts, bounds, rate;
 
-  for (int64_t s = 0; s < hp.n_subjects; ++s) {
-    for (int64_t oc = hp.subj_occ_off[s]; oc < hp.subj_occ_off[s + 1]; ++oc) {
-      const int64_t e0 = hp.occ_ev_off[oc], e1 = hp.occ_ev_off[oc + 1];
-      // initial_state: zeros, init only for occasion index 0 (analytical/mod.rs:409-426)
-      push(OP_RESET, hp.occ_index[oc] == 0 ? 1u : 0u, static_cast<double>(oc), 0.0, 0, nullptr, oc, 0.0, false);
-      const size_t reset_op = os->op_meta.size() - 1;
-      inf.clear();
-      if (n_slots > 0) {
-        // Lagged boluses leave the event list (the device merges them at t + lag(theta)); what remains is
-        // walked exactly like before.  ev_keep = indices of the remaining events, still sorted.
-        for (auto& v : lagb) v.clear();
-        double t_first = std::numeric_limits<double>::infinity();
-        uint32_t k_first = 3u;  // kind of the first remaining event (PMX_EV_*; 3 = none)
-        for (int64_t e = e0; e < e1; ++e) {
-          const bool lagged = hp.ev_kind[e] == PMX_EV_BOLUS && hp.ev_io[e] < PMX_MAX_INPUTS && slot_of_input[hp.ev_io[e]] >= 0;
-          if (lagged) {
-            max_input_used = std::max<int32_t>(max_input_used, hp.ev_io[e]);
-            lagb[slot_of_input[hp.ev_io[e]]].push_back({hp.ev_time[e], hp.ev_value[e], static_cast<int32_t>(hp.ev_io[e])});
-          } else if (k_first == 3u) {
-            t_first = hp.ev_time[e];
-            k_first = hp.ev_kind[e];
-          }
-        }
-        os->op_t0[reset_op] = t_first;
-        // ODE: which event is FIRST in the re-sorted list decides what is applied at the solver clock without integration
-        // (pmx_ode.hpp "the solver clock"); at equal times a bolus sorts behind an observation and in front of an infusion
-        // (event.rs:292-304).  Bits 25-26 of the RESET op = kind of the first remaining event.
-        os->op_meta[reset_op] |= k_first << 25;
-        for (int32_t k = 0; k < n_slots; ++k) {
-          for (const auto& tb : lagb[k]) {
-            os->lagb_time.push_back(tb.first);
-            os->lagb_amount.push_back(tb.second);
-            os->lagb_input.push_back(tb.input);
-          }
-          os->max_lagb_per_list = std::max<int64_t>(os->max_lagb_per_list, static_cast<int64_t>(lagb[k].size()));
-          os->lagb_off.push_back(static_cast<int64_t>(os->lagb_time.size()));
-        }
-      }
-      if (!ode) {
-        int64_t prev = -1;  // previous event that stays in the list
-        for (int64_t e = e0; e < e1; ++e) {  // simulate_event, equation/mod.rs:300-358
-          const uint8_t k = hp.ev_kind[e];
-          if (n_slots > 0 && k == PMX_EV_BOLUS && hp.ev_io[e] < PMX_MAX_INPUTS && slot_of_input[hp.ev_io[e]] >= 0) continue;
-          (void)prev;
-          if (k == PMX_EV_BOLUS) {
-            max_input_used = std::max<int32_t>(max_input_used, hp.ev_io[e]);
-            push(OP_BOLUS, hp.ev_io[e], hp.ev_value[e], hp.ev_time[e], 0, nullptr, oc, 0.0, false);  // (op_b: its time, for a user fa)
-          } else if (k == PMX_EV_INFUSION) {
-            inf.push_back({hp.ev_time[e], hp.ev_value[e], hp.ev_dur[e], static_cast<int32_t>(hp.ev_io[e])});
-          } else {
-            // Lag models: the lagged boluses are not in this list; the device merges them into the PROP steps at their
-            // landing times.  An observation that no PROP step precedes (events closer than the solve's 1e-12 dedup, or
-            // at the same instant) can still have a lagged bolus landing in front of it - a zero lag leaves the bolus
-            // where it was recorded, between two observations one ulp apart (found by the fuzz suite: seed 2235).  Bit 31
-            // tells the device to take the boluses landing before this observation's time first.
-            const bool flush = n_slots > 0 && !os->op_meta.empty() && (os->op_meta.back() & 0xffu) != OP_PROP;
-            push(OP_OBS, hp.ev_io[e], hp.ev_time[e], 0.0, 0, nullptr, oc, hp.ev_time[e], true);
-            if (flush) os->op_meta.back() |= (1u << 31);
-          }
-          int64_t en = e + 1;  // next event that stays in the list
-          if (n_slots > 0)
-            while (en < e1 && hp.ev_kind[en] == PMX_EV_BOLUS && hp.ev_io[en] < PMX_MAX_INPUTS &&
-                   slot_of_input[hp.ev_io[en]] >= 0)
-              ++en;
-          if (en < e1) {  // Analytical::solve, analytical/mod.rs:299-370
-            const double ti = hp.ev_time[e], tf = hp.ev_time[en];
-            if (ti == tf) continue;  // :308-310
-            ts.clear();
-            ts.push_back(ti);
-            ts.push_back(tf);
-            for (const auto& f : inf) {  // :316-325 strictly-inside breakpoints
-              const double t0 = f.time, t1 = t0 + f.duration;
-              if (t0 > ti && t0 < tf) ts.push_back(t0);
-              if (t1 > ti && t1 < tf) ts.push_back(t1);
-            }
-            std::sort(ts.begin(), ts.end());  // :326
-            {                                 // dedup_by |a-b| < 1e-12 against the last retained, :327
-              size_t w = 1;
-              for (size_t r = 1; r < ts.size(); ++r)
-                if (!(std::fabs(ts[r] - ts[w - 1]) < 1e-12)) ts[w++] = ts[r];
-              ts.resize(w);
-            }
-            double cur = ts[0];
-            for (size_t i = 1; i < ts.size(); ++i) {  // :334-367
-              const double nxt = ts[i];
-              double r0 = 0.0;  // rateiv[0]: the only slot the closed forms read
-              if (key.full_rates) std::fill(rate.begin(), rate.end(), 0.0);
-              for (const auto& f : inf) {
-                const double st = f.time, en = st + f.duration;
-                if (cur >= st && nxt <= en) {
-                  max_input_used = std::max(max_input_used, f.input);
-                  if (f.input == key.rate_input) r0 += f.amount / f.duration;  // :355
-                  if (key.full_rates && f.input < n_rate) rate[f.input] += f.amount / f.duration;
-                }
-              }
-              const double dt = nxt - cur;
-              const double t_cov = key.cov_time_mode == PMX_COV_TIME_SEGMENT_END_ABS ? nxt : dt;
-              push(OP_PROP, 0, dt, r0, 0, key.full_rates ? rate.data() : nullptr, oc, t_cov, true);
-              if (key.solve_marks && i > 1) os->op_meta.back() |= (1u << 24);  // a later sub-segment of the same solve
-              if (times) {
-                os->op_t0.back() = cur;
-                os->op_t1.back() = nxt;
-              }
-              os->n_prop++;
-              cur = nxt;
-            }
-          }
-        }
+  OccasionWalker(const HostPopulation& hp_, const CompileKey& key_, OpStream* os_)
+      : hp(hp_), key(key_), os(os_), lag(key_), w(hp_, key_, os_, lag.n_slots > 0 || key_.want_times),
+        rate(key_.n_rate > 0 ? key_.n_rate : 1, 0.0) {}
+
+  int32_t walk(int64_t occ, std::string* err) {
+    const int64_t e0 = hp.occ_ev_off[occ], e1 = hp.occ_ev_off[occ + 1];
+    const size_t reset_op = w.reset(occ);
+    inf.clear();
+    if (lag.n_slots > 0) lag.extract(hp, e0, e1, reset_op, os);
+    if (w.ode) return walk_ode(occ, e0, e1, reset_op, err);
+    walk_analytical(occ, e0, e1);
+    return PMX_OK;
+  }
+
+ private:
+  void push_infusion(int64_t e) { inf.push_back({hp.ev_time[e], hp.ev_value[e], hp.ev_dur[e], static_cast<int32_t>(hp.ev_io[e])}); }
+
+  void walk_analytical(int64_t occ, int64_t e0, int64_t e1) {  // simulate_event, equation/mod.rs:300-358
+    for (int64_t e = lag.next_kept(hp, e0, e1); e < e1;) {
+      const uint8_t k = hp.ev_kind[e];
+      if (k == PMX_EV_BOLUS) {
+        w.bolus(e);
+      } else if (k == PMX_EV_INFUSION) {
+        push_infusion(e);
       } else {
-        // ODE::run_events (ode/mod.rs:609-823) with InfusionSchedule over ALL infusions
-        // of the occasion (closure.rs:109-180).
-        bounds.clear();
-        for (int64_t e = e0; e < e1; ++e) {
-          if (hp.ev_kind[e] != PMX_EV_INFUSION) continue;
-          if (hp.ev_dur[e] <= 0.0) continue;  // closure.rs:127-129
-          max_input_used = std::max<int32_t>(max_input_used, hp.ev_io[e]);
-          inf.push_back({hp.ev_time[e], hp.ev_value[e], hp.ev_dur[e], static_cast<int32_t>(hp.ev_io[e])});
-          bounds.push_back(hp.ev_time[e]);
-          bounds.push_back(hp.ev_time[e] + hp.ev_dur[e]);
-        }
-        std::sort(bounds.begin(), bounds.end());
-        bounds.erase(std::unique(bounds.begin(), bounds.end()), bounds.end());  // exact dedup, closure.rs:143-148
-        auto is_lagged = [&](int64_t e) {
-          return n_slots > 0 && hp.ev_kind[e] == PMX_EV_BOLUS && hp.ev_io[e] < PMX_MAX_INPUTS && slot_of_input[hp.ev_io[e]] >= 0;
-        };
-        // The solver clock starts at Occasion::initial_time() of the occasion AS RECORDED - lagged boluses at their
-        // recorded times included (ode/mod.rs:348 takes it from the occasion, not from the lag-rewritten event list;
-        // structs.rs:782-793) - and only moves forward to the time of the next event (ode/mod.rs:719-721).  PROP ops
-        // therefore start there; a lane whose own clock is ahead (boluses that landed before the first remaining event
-        // took it there) starts its piece at its clock (pmx_ode.hpp / pmx_ode_user.hpp).  RESET: op_b = that time.
-        double t = 0.0;
-        for (int64_t e = e0; e < e1; ++e) t = (e == e0) ? hp.ev_time[e] : std::min(t, hp.ev_time[e]);
-        os->op_b[reset_op] = t;
-        size_t bcur = 0;
-        for (int64_t e = e0; e < e1; ++e) {
-          const uint8_t k = hp.ev_kind[e];
-          if (is_lagged(e)) continue;
-          if (k == PMX_EV_BOLUS) {
-            max_input_used = std::max<int32_t>(max_input_used, hp.ev_io[e]);
-            push(OP_BOLUS, hp.ev_io[e], hp.ev_value[e], hp.ev_time[e], 0, nullptr, oc, 0.0, false);  // (op_b: its time, for a user fa / bolus jump)
-          } else if (k == PMX_EV_OBSERVATION) {
-            push(OP_OBS, hp.ev_io[e], hp.ev_time[e], 0.0, 0, nullptr, oc, hp.ev_time[e], true);
-          }
-          int64_t en = e + 1;
-          while (en < e1 && is_lagged(en)) ++en;
-          if (en < e1) {
-            const double next_t = hp.ev_time[en];
-            while (next_t > t) {  // ode/mod.rs:721-739
-              while (bcur < bounds.size() && bounds[bcur] <= t) ++bcur;
-              double stop = next_t;
-              if (bcur < bounds.size() && bounds[bcur] <= next_t) stop = bounds[bcur++];
-              std::fill(rate.begin(), rate.end(), 0.0);
-              for (const auto& f : inf) {  // right-continuous rate at t (closure.rs:80-99)
-                const double st = f.time, en = st + f.duration;
-                if (st <= t && t < en && f.input < n_rate) rate[f.input] += f.amount / f.duration;
-              }
-              const double dt = stop - t;
-              if (dt > 0.0) {
-                double nf = std::ceil(dt / key.rk4_h_max);
-                if (nf < 1.0) nf = 1.0;
-                if (nf > 2.0e9) {
-                  *err = "RK4 step count overflow (dt / rk4_h_max too large)";
-                  return PMX_ERR_INVALID_ARGUMENT;
-                }
-                const int32_t n = static_cast<int32_t>(nf);
-                push(OP_PROP, 0, dt, dt / static_cast<double>(n), n, rate.data(), oc, t, true);
-                if (times) {
-                  os->op_t0.back() = t;
-                  os->op_t1.back() = stop;
-                }
-                os->n_prop++;
-              }
-              t = stop;
-            }
-          }
-        }
+        // Lag models: the lagged boluses are not in this list; the device merges them into the PROP steps at their
+        // landing times.  An observation that no PROP step precedes (events closer than the solve's 1e-12 dedup, or
+        // at the same instant) can still have a lagged bolus landing in front of it - a zero lag leaves the bolus
+        // where it was recorded, between two observations one ulp apart (found by the fuzz suite: seed 2235).  Flush
+        // tells the device to take the boluses landing before this observation's time first.
+        const bool flush = lag.n_slots > 0 && op_kind(os->op_meta.back()) != OP_PROP;
+        w.obs(occ, e);
+        if (flush) os->op_meta.back() |= 1u << kOpFlushShift;
       }
-    }
-    os->subj_op_off[s + 1] = static_cast<int64_t>(os->op_meta.size());
-    if (key.prop_cache_slots > 0 && !ode && !os->op_fac.empty()) {
-      // Propagator reuse for covariate-derived rate constants.  The macro lowering evaluates `derive` at the segment
-      // LENGTH (expand/analytical.rs:254,286), so two PROPs of equal length see equal covariates, hence equal rate
-      // constants and the same transition matrix (a subject-constant covariate gives the same under either rule).
-      // Per occasion: key = (dt, factor row) bitwise; a key with a later use gets a slot (furthest-next-use eviction);
-      // code 1 + k = build and keep in slot k, 1 + S + k = take slot k (S = prop_cache_slots), 0 = build.
-      const int32_t NS_ = key.prop_cache_slots;
-      const size_t nfac = static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS;
-      const int64_t o0 = os->subj_op_off[s], o1 = os->subj_op_off[s + 1];
-      auto same = [&](int64_t a, int64_t b) {
-        return std::memcmp(&os->op_a[a], &os->op_a[b], 8) == 0 && (os->op_b[a] != 0.0) == (os->op_b[b] != 0.0) &&  // (rate-free
-               // segments keep the transition part only: they share among themselves, segments under an infusion likewise)
-               std::memcmp(&os->op_fac[static_cast<size_t>(a) * nfac], &os->op_fac[static_cast<size_t>(b) * nfac], nfac * 8) == 0;
-      };
-      int64_t seg0 = o0;
-      while (seg0 < o1) {  // one occasion at a time (a RESET re-derives the lane's failure state)
-        int64_t seg1 = seg0 + 1;
-        while (seg1 < o1 && (os->op_meta[seg1] & 0xffu) != OP_RESET) ++seg1;
-        std::vector<int64_t> props;
-        for (int64_t o = seg0; o < seg1; ++o)
-          if ((os->op_meta[o] & 0xffu) == OP_PROP) props.push_back(o);
-        const size_t n = props.size();
-        std::vector<int64_t> next(n, -1);  // index (into props) of the next PROP with the same key
-        for (size_t i = 0; i < n; ++i)
-          for (size_t j = i + 1; j < n; ++j)
-            if (same(props[i], props[j])) {
-              next[i] = static_cast<int64_t>(j);
-              break;
-            }
-        int64_t last_built = -1;
-        std::vector<int64_t> holder(static_cast<size_t>(NS_), -1);  // slot -> index of the PROP whose propagator it holds
-        std::vector<int32_t> slot_of(n, -1);
-        for (size_t i = 0; i < n; ++i) {
-          int32_t from = -1;
-          for (int32_t k = 0; k < NS_; ++k)
-            if (holder[static_cast<size_t>(k)] >= 0 && next[static_cast<size_t>(holder[static_cast<size_t>(k)])] == static_cast<int64_t>(i)) from = k;
-          uint32_t code = 0;
-          if (from >= 0) {  // take it; the slot now stands for this PROP (same key, next use continues the chain)
-            code = static_cast<uint32_t>(1 + NS_ + from);
-            holder[static_cast<size_t>(from)] = next[i] >= 0 ? static_cast<int64_t>(i) : -1;
-            os->n_prop_reused++;
-            os->prop_cache_used = std::max(os->prop_cache_used, from + 1);
-          } else if (next[i] >= 0) {  // first of several: keep it if a slot is free or holds something needed later than this
-            int32_t pick = -1;
-            int64_t worst = -1;
-            for (int32_t k = 0; k < NS_; ++k) {
-              const int64_t h = holder[static_cast<size_t>(k)];
-              if (h < 0) {
-                pick = k;
-                worst = std::numeric_limits<int64_t>::max();
-                break;
-              }
-              if (next[static_cast<size_t>(h)] > worst) {
-                worst = next[static_cast<size_t>(h)];
-                pick = k;
-              }
-            }
-            if (pick >= 0 && (holder[static_cast<size_t>(pick)] < 0 || worst > next[i])) {
-              holder[static_cast<size_t>(pick)] = static_cast<int64_t>(i);
-              code = static_cast<uint32_t>(1 + pick);
-            }
-          }
-          os->op_meta[props[i]] |= code << 24;
-          // bit 27: this PROP's covariate factor row equals the one of the occasion's previous BUILT PROP (a subject-constant
-          // covariate: every segment) - the rate constants, hence the eigenvalues, are the same and only the step length
-          // differs (pmx_analytical_dyn3 keeps the last eigenvalues in registers).  "Built" = not taken from a slot.
-          if (code <= static_cast<uint32_t>(NS_)) {
-            if (last_built >= 0 && std::memcmp(&os->op_fac[static_cast<size_t>(props[i]) * nfac],
-                                               &os->op_fac[static_cast<size_t>(last_built) * nfac], nfac * 8) == 0)
-              os->op_meta[props[i]] |= 1u << 27;
-            last_built = props[i];
-          }
-        }
-        seg0 = seg1;
-      }
-    }
-    if (key.ladder && !ode) {  // exponential ladder along the subject's PROP ops (the lane's rate constants never change)
-      double prev = 0.0, span = 1.0;
-      for (int64_t o = os->subj_op_off[s]; o < os->subj_op_off[s + 1]; ++o)
-        if ((os->op_meta[o] & 0xffu) == OP_PROP) os->op_meta[o] |= ladder_code(os->op_a[o], &prev, &span) << 27;
+      const int64_t en = lag.next_kept(hp, e + 1, e1);
+      if (en < e1) solve_analytical(occ, hp.ev_time[e], hp.ev_time[en]);
+      e = en;
     }
   }
-  if (cov_missing) {
+
+  // Analytical::solve over [ti, tf] (analytical/mod.rs:299-370): one PROP per constant-rate sub-segment
+  void solve_analytical(int64_t occ, double ti, double tf) {
+    if (ti == tf) return;  // :308-310
+    ts.clear();
+    ts.push_back(ti);
+    ts.push_back(tf);
+    for (const auto& f : inf) {  // :316-325 strictly-inside breakpoints
+      const double t0 = f.time, t1 = t0 + f.duration;
+      if (t0 > ti && t0 < tf) ts.push_back(t0);
+      if (t1 > ti && t1 < tf) ts.push_back(t1);
+    }
+    std::sort(ts.begin(), ts.end());  // :326
+    size_t n = 1;                     // dedup_by |a-b| < 1e-12 against the last retained, :327
+    for (size_t r = 1; r < ts.size(); ++r)
+      if (!(std::fabs(ts[r] - ts[n - 1]) < 1e-12)) ts[n++] = ts[r];
+    for (size_t i = 1; i < n; ++i) {  // :334-367
+      const double cur = ts[i - 1], nxt = ts[i];
+      double r0 = 0.0;  // rateiv[0]: the only slot the closed forms read
+      if (key.full_rates) std::fill(rate.begin(), rate.end(), 0.0);
+      for (const auto& f : inf) {
+        const double st = f.time, en = st + f.duration;
+        if (cur >= st && nxt <= en) {
+          os->max_input_used = std::max(os->max_input_used, f.input);
+          if (f.input == key.rate_input) r0 += f.amount / f.duration;  // :355
+          if (key.full_rates && f.input < key.n_rate) rate[f.input] += f.amount / f.duration;
+        }
+      }
+      const double t_cov = key.cov_time_mode == PMX_COV_TIME_SEGMENT_END_ABS ? nxt : nxt - cur;
+      w.prop(occ, cur, nxt, r0, 0, key.full_rates ? rate.data() : nullptr, t_cov);
+      if (key.solve_marks && i > 1) os->op_meta.back() |= 1u << kOpContinuesShift;
+    }
+  }
+
+  // ODE::run_events (ode/mod.rs:609-823) with InfusionSchedule over ALL infusions of the occasion (closure.rs:109-180)
+  int32_t walk_ode(int64_t occ, int64_t e0, int64_t e1, size_t reset_op, std::string* err) {
+    bounds.clear();
+    for (int64_t e = e0; e < e1; ++e) {
+      if (hp.ev_kind[e] != PMX_EV_INFUSION) continue;
+      if (hp.ev_dur[e] <= 0.0) continue;  // closure.rs:127-129
+      os->max_input_used = std::max<int32_t>(os->max_input_used, hp.ev_io[e]);
+      push_infusion(e);
+      bounds.push_back(hp.ev_time[e]);
+      bounds.push_back(hp.ev_time[e] + hp.ev_dur[e]);
+    }
+    std::sort(bounds.begin(), bounds.end());
+    bounds.erase(std::unique(bounds.begin(), bounds.end()), bounds.end());  // exact dedup, closure.rs:143-148
+    // The solver clock starts at Occasion::initial_time() of the occasion AS RECORDED - lagged boluses at their
+    // recorded times included (ode/mod.rs:348 takes it from the occasion, not from the lag-rewritten event list;
+    // structs.rs:782-793) - and only moves forward to the time of the next event (ode/mod.rs:719-721).  PROP ops
+    // therefore start there; a lane whose own clock is ahead (boluses that landed before the first remaining event
+    // took it there) starts its piece at its clock (pmx_ode.hpp / pmx_ode_user.hpp).  RESET: op_b = that time.
+    double t = 0.0;
+    for (int64_t e = e0; e < e1; ++e) t = (e == e0) ? hp.ev_time[e] : std::min(t, hp.ev_time[e]);
+    os->op_b[reset_op] = t;
+    size_t bcur = 0;
+    for (int64_t e = lag.next_kept(hp, e0, e1); e < e1;) {
+      if (hp.ev_kind[e] == PMX_EV_BOLUS) w.bolus(e);
+      if (hp.ev_kind[e] == PMX_EV_OBSERVATION) w.obs(occ, e);
+      const int64_t en = lag.next_kept(hp, e + 1, e1);
+      const double next_t = en < e1 ? hp.ev_time[en] : t;
+      while (next_t > t) {  // ode/mod.rs:721-739
+        while (bcur < bounds.size() && bounds[bcur] <= t) ++bcur;
+        double stop = next_t;
+        if (bcur < bounds.size() && bounds[bcur] <= next_t) stop = bounds[bcur++];
+        std::fill(rate.begin(), rate.end(), 0.0);
+        for (const auto& f : inf)  // right-continuous rate at t (closure.rs:80-99)
+          if (f.time <= t && t < f.time + f.duration && f.input < key.n_rate) rate[f.input] += f.amount / f.duration;
+        const double dt = stop - t;
+        if (dt > 0.0) {
+          double nf = std::ceil(dt / key.rk4_h_max);
+          if (nf < 1.0) nf = 1.0;
+          if (nf > 2.0e9) {
+            *err = "RK4 step count overflow (dt / rk4_h_max too large)";
+            return PMX_ERR_INVALID_ARGUMENT;
+          }
+          const int32_t n = static_cast<int32_t>(nf);
+          w.prop(occ, t, stop, dt / static_cast<double>(n), n, rate.data(), t);
+        }
+        t = stop;
+      }
+      e = en;
+    }
+    return PMX_OK;
+  }
+};
+
+// Propagator reuse for covariate-derived rate constants, one occasion's PROP ops `props` at a time (a RESET re-derives
+// the lane's failure state).  The macro lowering evaluates `derive` at the segment LENGTH (expand/analytical.rs:254,286),
+// so two PROPs of equal length see equal covariates, hence equal rate constants and the same transition matrix (a
+// subject-constant covariate gives the same under either rule).  Key = (dt, factor row) bitwise; a key with a later
+// use gets a slot (furthest-next-use eviction).  Cache code: 1 + k = build and keep in slot k, 1 + S + k = take slot k
+// (S = prop_cache_slots), 0 = build.
+void code_prop_cache(const std::vector<int64_t>& props, int32_t n_slots, size_t nfac, OpStream* os) {
+  auto same_row = [&](int64_t a, int64_t b) {
+    return std::memcmp(&os->op_fac[static_cast<size_t>(a) * nfac], &os->op_fac[static_cast<size_t>(b) * nfac], nfac * 8) == 0;
+  };
+  auto same = [&](int64_t a, int64_t b) {  // (rate-free segments keep the transition part only: they share among
+    // themselves, segments under an infusion likewise)
+    return std::memcmp(&os->op_a[a], &os->op_a[b], 8) == 0 && (os->op_b[a] != 0.0) == (os->op_b[b] != 0.0) && same_row(a, b);
+  };
+  const size_t n = props.size();
+  std::vector<int64_t> next(n, -1);  // index (into props) of the next PROP with the same key
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = i + 1; j < n; ++j)
+      if (same(props[i], props[j])) {
+        next[i] = static_cast<int64_t>(j);
+        break;
+      }
+  int64_t last_built = -1;
+  std::vector<int64_t> holder(static_cast<size_t>(n_slots), -1);  // slot -> index of the PROP whose propagator it holds
+  for (size_t i = 0; i < n; ++i) {
+    int32_t from = -1;
+    for (int32_t k = 0; k < n_slots; ++k)
+      if (holder[k] >= 0 && next[static_cast<size_t>(holder[k])] == static_cast<int64_t>(i)) from = k;
+    uint32_t code = 0;
+    if (from >= 0) {  // take it; the slot now stands for this PROP (same key, next use continues the chain)
+      code = static_cast<uint32_t>(1 + n_slots + from);
+      holder[from] = next[i] >= 0 ? static_cast<int64_t>(i) : -1;
+      os->n_prop_reused++;
+      os->prop_cache_used = std::max(os->prop_cache_used, from + 1);
+    } else if (next[i] >= 0) {  // first of several: keep it if a slot is free or holds something needed later than this
+      int32_t pick = -1;
+      int64_t worst = -1;
+      for (int32_t k = 0; k < n_slots; ++k) {
+        const int64_t h = holder[k];
+        if (h < 0) {
+          pick = k;
+          worst = std::numeric_limits<int64_t>::max();
+          break;
+        }
+        if (next[static_cast<size_t>(h)] > worst) {
+          worst = next[static_cast<size_t>(h)];
+          pick = k;
+        }
+      }
+      if (pick >= 0 && (holder[pick] < 0 || worst > next[i])) {
+        holder[pick] = static_cast<int64_t>(i);
+        code = static_cast<uint32_t>(1 + pick);
+      }
+    }
+    os->op_meta[props[i]] |= code << kOpCacheShift;
+    // SameFac: this PROP's covariate factor row equals the one of the occasion's previous BUILT PROP (a subject-constant
+    // covariate: every segment) - the rate constants, hence the eigenvalues, are the same and only the step length
+    // differs (pmx_analytical_dyn3 keeps the last eigenvalues in registers).  "Built" = not taken from a slot.
+    if (code <= static_cast<uint32_t>(n_slots)) {
+      if (last_built >= 0 && same_row(props[i], last_built)) os->op_meta[props[i]] |= kOpSameFacBit;
+      last_built = props[i];
+    }
+  }
+}
+
+// cache codes of the ops [o0, o1) of one subject, occasion by occasion
+void code_prop_cache_of_subject(const CompileKey& key, int64_t o0, int64_t o1, OpStream* os) {
+  const size_t nfac = static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS;
+  std::vector<int64_t> props;
+  for (int64_t o = o0; o <= o1; ++o) {
+    if (o == o1 || op_kind(os->op_meta[o]) == OP_RESET) {
+      code_prop_cache(props, key.prop_cache_slots, nfac, os);
+      props.clear();
+    } else if (op_kind(os->op_meta[o]) == OP_PROP) {
+      props.push_back(o);
+    }
+  }
+}
+
+// exponential ladder along one subject's PROP ops (the lane's rate constants never change)
+void code_ladder(int64_t o0, int64_t o1, OpStream* os) {
+  double prev = 0.0, span = 1.0;
+  for (int64_t o = o0; o < o1; ++o)
+    if (op_kind(os->op_meta[o]) == OP_PROP) os->op_meta[o] |= ladder_code(os->op_a[o], &prev, &span) << kOpRungShift;
+}
+
+// lane-per-pair kernels: neighbours in a wavefront should have similar op counts (ODE: RK4 step counts)
+void order_subjects(int64_t n_subjects, OpStream* os) {
+  std::vector<int64_t> work(n_subjects);
+  int64_t longest = 0;
+  for (int64_t s = 0; s < n_subjects; ++s) {
+    const int64_t o0 = os->subj_op_off[s], o1 = os->subj_op_off[s + 1];
+    work[s] = o1 - o0;
+    for (int64_t o = o0; o < o1 && !os->op_n.empty(); ++o) work[s] += os->op_n[o];
+    longest = std::max(longest, o1 - o0);
+  }
+  os->subj_order.resize(n_subjects);
+  std::iota(os->subj_order.begin(), os->subj_order.end(), 0);
+  std::stable_sort(os->subj_order.begin(), os->subj_order.end(), [&](int32_t a, int32_t b) { return work[a] > work[b]; });
+  os->max_ops_per_subject = static_cast<int32_t>(longest);
+}
+
+}  // namespace
+
+int32_t compile_ops(const HostPopulation& hp, const CompileKey& key, OpStream* os, std::string* err) {
+  *os = OpStream{};
+  os->key = key;
+  os->subj_op_off.assign(hp.n_subjects + 1, 0);
+  OccasionWalker walker(hp, key, os);
+  os->n_lag_slots = walker.lag.n_slots;
+  if (os->n_lag_slots > 0) os->lagb_off.push_back(0);
+  const bool analytical = key.eq_kind != PMX_EQ_ODE;
+  for (int64_t s = 0; s < hp.n_subjects; ++s) {
+    for (int64_t occ = hp.subj_occ_off[s]; occ < hp.subj_occ_off[s + 1]; ++occ) {
+      const int32_t rc = walker.walk(occ, err);
+      if (rc != PMX_OK) return rc;
+    }
+    const int64_t o0 = os->subj_op_off[s], o1 = static_cast<int64_t>(os->op_meta.size());
+    os->subj_op_off[s + 1] = o1;
+    if (analytical && key.prop_cache_slots > 0 && !os->op_fac.empty()) code_prop_cache_of_subject(key, o0, o1, os);
+    if (analytical && key.ladder) code_ladder(o0, o1, os);
+  }
+  if (walker.w.cov_missing) {
     *err = "covariate interpolation failed (MissingSegments)";
     return PMX_ERR_INVALID_ARGUMENT;
   }
   os->n_ops = static_cast<int64_t>(os->op_meta.size());
-  // lane-per-pair kernels: neighbours in a wavefront should have similar op counts
-  os->subj_order.resize(hp.n_subjects);
-  std::iota(os->subj_order.begin(), os->subj_order.end(), 0);
-  auto work = [&](int32_t s) -> int64_t {
-    if (!ode) return os->subj_op_off[s + 1] - os->subj_op_off[s];
-    int64_t w = 0;
-    for (int64_t o = os->subj_op_off[s]; o < os->subj_op_off[s + 1]; ++o) w += 1 + os->op_n[o];
-    return w;
-  };
-  std::vector<int64_t> wk(hp.n_subjects);
-  for (int64_t s = 0; s < hp.n_subjects; ++s) wk[s] = work(static_cast<int32_t>(s));
-  std::stable_sort(os->subj_order.begin(), os->subj_order.end(), [&](int32_t a, int32_t b) { return wk[a] > wk[b]; });
-  int64_t mx = 0;
-  for (int64_t s = 0; s < hp.n_subjects; ++s) mx = std::max(mx, os->subj_op_off[s + 1] - os->subj_op_off[s]);
-  os->max_ops_per_subject = static_cast<int32_t>(mx);
-  os->max_input_used = max_input_used;
-  return PMX_OK;
-}
-
-}  // namespace pmx
-
-// ------------------------------------------------------------------------------------
-// class plan
-// ------------------------------------------------------------------------------------
-#include <unordered_map>
-
-namespace pmx {
-
-namespace {
-inline uint64_t mix64(uint64_t h, uint64_t v) {
-  h ^= v + 0x9E3779B97F4A7C15ULL + (h << 6) + (h >> 2);
-  h *= 0xBF58476D1CE4E5B9ULL;
-  return h ^ (h >> 31);
-}
-}  // namespace
-
-void build_step_stream(const OpStream& os, std::vector<int64_t>* subj_step_off, std::vector<double>* rec) {
-  const int64_t S = static_cast<int64_t>(os.subj_op_off.size()) - 1;
-  subj_step_off->assign(static_cast<size_t>(S) + 1, 0);
-  rec->clear();
-  rec->reserve(static_cast<size_t>(os.n_ops) * 2 + 4);
-  auto push = [&](uint64_t meta, double a, double b) {
-    double w;
-    std::memcpy(&w, &meta, 8);
-    rec->push_back(w);
-    rec->push_back(a);
-    rec->push_back(b);
-    rec->push_back(0.0);
-  };
-  int64_t n_steps = 0;
-  for (int64_t s = 0; s < S; ++s) {
-    int64_t last = -1;  // this subject's last step, if it can still take an observation
-    for (int64_t o = os.subj_op_off[s]; o < os.subj_op_off[s + 1]; ++o) {
-      const uint32_t meta = os.op_meta[o];
-      const uint32_t kind = meta & 0xffu, io = (meta >> 8) & 0xffffu;
-      if (kind == OP_OBS) {
-        const uint64_t tag = (1ull << 24) | (static_cast<uint64_t>(io & 3u) << 25);
-        if (last >= 0) {
-          uint64_t w;
-          std::memcpy(&w, &(*rec)[static_cast<size_t>(last) * 4], 8);
-          w |= tag;
-          std::memcpy(&(*rec)[static_cast<size_t>(last) * 4], &w, 8);
-          last = -1;
-        } else {
-          push(static_cast<uint64_t>(OP_OBS) | tag, 0.0, 0.0);
-          ++n_steps;
-        }
-      } else {
-        // kind | io | the PROP's ladder rung (bits 27-29 of the op, pmx_compile.cpp ladder_code)
-        push(static_cast<uint64_t>(kind) | (static_cast<uint64_t>(io) << 8) | (static_cast<uint64_t>(meta) & (7ull << 27)), os.op_a[o],
-             os.op_b[o]);
-        last = n_steps++;
-      }
-    }
-    (*subj_step_off)[static_cast<size_t>(s) + 1] = n_steps;
-  }
-  push(static_cast<uint64_t>(OP_OBS), 0.0, 0.0);  // padding: the walker requests one record past a subject's last step
-}
-
-uint32_t ladder_code(double dt, double* prev, double* span) {
-  uint32_t code = 0;
-  if (*prev > 0.0 && dt > 0.0) {
-    for (uint32_t n = 1; n <= 4; ++n) {
-      if (std::fabs(dt - n * *prev) <= 8.0 * std::numeric_limits<double>::epsilon() * dt && *span * n <= 1024.0) {
-        code = n;
-        break;
-      }
-    }
-  }
-  if (code) {
-    *span *= code;
-    *prev = code * *prev;
-  } else {
-    *span = 1.0;
-    *prev = dt;
-  }
-  return code;
-}
-
-void build_class_plan(const HostPopulation& hp, const OpStream& os, int32_t G, int32_t min_class_size, ClassPlan* cp,
-                      bool ladder, bool spread, bool loose_classes) {
-  *cp = ClassPlan{};
-  cp->G = G;
-  const int64_t S = hp.n_subjects;
-  const bool dyn = os.key.n_derived > 0 && !os.op_fac.empty();  // covariate-derived constants: nothing to share but the program shape
-  const size_t nfac = static_cast<size_t>(os.key.n_derived) * PMX_MAX_FACTORS;
-  cp->n_fac = static_cast<int32_t>(nfac);
-  if (dyn) loose_classes = true;
-  const bool lagged = os.n_lag_slots == 1;  // (the caller only asks for a plan of a lag model when one input is lagged)
-  if (os.n_lag_slots > 1) return;
-  if (lagged) loose_classes = false;  // loose members do not share the times
-  auto sig_key = [&](int64_t o) -> uint64_t {  // what must match between class members, per op
-    const uint32_t kind = os.op_meta[o] & 0xffu;
-    uint64_t bits = 0;
-    if (kind == OP_PROP) std::memcpy(&bits, &os.op_a[o], 8);  // dt; BOLUS amount / PROP rate / OBS time are free
-    return (static_cast<uint64_t>(os.op_meta[o]) << 1) ^ (bits * 0x9E3779B97F4A7C15ULL) ^ bits;
-  };
-  auto same_program = [&](int64_t a, int64_t b) {
-    const int64_t a0 = os.subj_op_off[a], a1 = os.subj_op_off[a + 1];
-    const int64_t b0 = os.subj_op_off[b], b1 = os.subj_op_off[b + 1];
-    if (a1 - a0 != b1 - b0) return false;
-    for (int64_t i = 0; i < a1 - a0; ++i) {
-      if (os.op_meta[a0 + i] != os.op_meta[b0 + i]) return false;
-      const uint32_t kind = os.op_meta[a0 + i] & 0xffu;
-      if (kind == OP_PROP && std::memcmp(&os.op_a[a0 + i], &os.op_a[b0 + i], 8) != 0) return false;
-      if (lagged) {  // members of a lag class also share every absolute time a lane's lagged boluses are compared with
-        if (kind == OP_PROP && (std::memcmp(&os.op_t0[a0 + i], &os.op_t0[b0 + i], 8) != 0 ||
-                                std::memcmp(&os.op_t1[a0 + i], &os.op_t1[b0 + i], 8) != 0))
-          return false;
-        if (kind == OP_RESET) {
-          if (std::memcmp(&os.op_t0[a0 + i], &os.op_t0[b0 + i], 8) != 0) return false;
-          const int64_t oa = static_cast<int64_t>(os.op_a[a0 + i]), ob = static_cast<int64_t>(os.op_a[b0 + i]);
-          const int64_t la = os.lagb_off[oa], lb = os.lagb_off[ob];
-          const int64_t na = os.lagb_off[oa + 1] - la;
-          if (na != os.lagb_off[ob + 1] - lb) return false;
-          if (na > 0 && std::memcmp(&os.lagb_time[la], &os.lagb_time[lb], static_cast<size_t>(na) * 8) != 0) return false;
-        }
-      }
-    }
-    return true;
-  };
-  // class id per subject (representative = first subject seen with that program)
-  std::unordered_map<uint64_t, std::vector<int32_t>> buckets;  // hash -> class ids
-  std::vector<int32_t> cls_rep;                                 // class -> representative subject
-  std::vector<std::vector<int32_t>> members;
-  for (int64_t s = 0; s < S; ++s) {
-    const int64_t o0 = os.subj_op_off[s], o1 = os.subj_op_off[s + 1];
-    if (o1 == o0) {  // an empty subject: nothing to compute, but the generic walker still owns its status bytes
-      cp->generic_subjects.push_back(static_cast<int32_t>(s));
-      continue;
-    }
-    if (os.key.rate_input == 1) {  // pm_ indexing: a bolus into input 0 lands in the wrapper's pad slot (generic walker only)
-      bool pad_dose = false;
-      for (int64_t o = o0; o < o1; ++o)
-        if ((os.op_meta[o] & 0xffu) == OP_BOLUS && ((os.op_meta[o] >> 8) & 0xffffu) == 0u) pad_dose = true;
-      if (pad_dose) {
-        cp->generic_subjects.push_back(static_cast<int32_t>(s));
-        continue;
-      }
-    }
-    uint64_t h = static_cast<uint64_t>(o1 - o0);
-    for (int64_t o = o0; o < o1; ++o) {
-      h = mix64(h, sig_key(o));
-      if (lagged) {
-        uint64_t bits = 0;
-        std::memcpy(&bits, &os.op_t0[o], 8);
-        h = mix64(h, bits);
-        if ((os.op_meta[o] & 0xffu) == OP_RESET) {
-          const int64_t oc = static_cast<int64_t>(os.op_a[o]);
-          for (int64_t q = os.lagb_off[oc]; q < os.lagb_off[oc + 1]; ++q) {
-            std::memcpy(&bits, &os.lagb_time[q], 8);
-            h = mix64(h, bits);
-          }
-        }
-      }
-    }
-    auto& ids = buckets[h];
-    int32_t cls = -1;
-    for (int32_t c : ids)
-      if (same_program(cls_rep[c], s)) {
-        cls = c;
-        break;
-      }
-    if (cls < 0) {
-      cls = static_cast<int32_t>(cls_rep.size());
-      cls_rep.push_back(static_cast<int32_t>(s));
-      members.emplace_back();
-      ids.push_back(cls);
-    }
-    members[cls].push_back(static_cast<int32_t>(s));
-  }
-  cp->cls_prog_off.push_back(0);
-  int32_t out_cls = 0;
-  // one class -> its program and its chunks; `loose`: the members' PROP lengths differ (dtv), no ladder
-  auto emit_class = [&](const std::vector<int32_t>& mem, int32_t rep, bool loose) {
-    const int64_t r0 = os.subj_op_off[rep], r1 = os.subj_op_off[rep + 1];
-    // Program steps: every OBS op is FUSED into the step before it (bit 24 = "emit a row after this step",
-    // bits 25-26 = its outeq), so a PROP+OBS pair costs one trip of the device loop.  A second observation
-    // at the same instant gets a step of its own (kind OP_OBS = no state change).
-    std::vector<int32_t> step_of_op(static_cast<size_t>(r1 - r0), -1);
-    std::vector<int32_t> obs_step_of_op(static_cast<size_t>(r1 - r0), -1);  // OBS op -> the step that emits its row
-    std::vector<uint32_t> step_meta;
-    std::vector<double> step_dt, step_t0, step_t1;
-    for (int64_t o = r0; o < r1; ++o) {
-      const uint32_t kind = os.op_meta[o] & 0xffu;
-      const uint32_t io = (os.op_meta[o] >> 8) & 0xffffu;
-      if (kind == OP_OBS) {
-        const uint32_t flush = os.op_meta[o] & (1u << 31);  // lag models: lagged boluses may land in front of it (see above)
-        if (!step_meta.empty() && ((step_meta.back() >> 24) & 1u) == 0u) {
-          step_meta.back() |= (1u << 24) | ((io & 3u) << 25) | flush;
-          if (flush) step_t1.back() = os.op_a[o];  // (never a PROP step: its t1 slot is free) the observation's time
-          obs_step_of_op[static_cast<size_t>(o - r0)] = static_cast<int32_t>(step_meta.size()) - 1;
-        } else {
-          obs_step_of_op[static_cast<size_t>(o - r0)] = static_cast<int32_t>(step_meta.size());
-          step_meta.push_back(make_meta(OP_OBS, 0) | (1u << 24) | ((io & 3u) << 25) | flush);
-          step_dt.push_back(0.0);
-          step_t0.push_back(0.0);
-          step_t1.push_back(flush ? os.op_a[o] : 0.0);
-        }
-      } else {
-        step_meta.push_back(make_meta(kind, io));
-        step_dt.push_back(kind == OP_PROP ? os.op_a[o] : 0.0);
-        step_t0.push_back(lagged ? os.op_t0[o] : 0.0);
-        step_t1.push_back(lagged ? os.op_t1[o] : 0.0);
-        step_of_op[static_cast<size_t>(o - r0)] = static_cast<int32_t>(step_meta.size()) - 1;
-      }
-    }
-    const int64_t L = static_cast<int64_t>(step_meta.size());
-    if (ladder && !loose) {
-      // Exponential ladder (pmx_structures.hpp ladder_pow): bits 27-29 of a PROP step = n when its length is
-      // n x the previous PROP's (n = 1: same propagator again).  `span` = how many times the first rung's
-      // rounding error has been multiplied; past 1024 the next step starts a fresh ladder.
-      double prev = 0.0, span = 1.0;
-      for (int64_t i = 0; i < L; ++i) {
-        if ((step_meta[static_cast<size_t>(i)] & 0xffu) != OP_PROP) continue;
-        step_meta[static_cast<size_t>(i)] |= ladder_code(step_dt[static_cast<size_t>(i)], &prev, &span) << 27;
-      }
-    }
-    for (int64_t i = 0; i < L; ++i) {
-      cp->prog_meta.push_back(step_meta[static_cast<size_t>(i)]);
-      cp->prog_dt.push_back(loose ? 0.0 : step_dt[static_cast<size_t>(i)]);
-      cp->prog_t0.push_back(step_t0[static_cast<size_t>(i)]);
-      cp->prog_t1.push_back(step_t1[static_cast<size_t>(i)]);
-    }
-    cp->cls_prog_off.push_back(static_cast<int64_t>(cp->prog_meta.size()));
-    {
-      uint64_t fast = 0;
-      for (int64_t i = 0; i < L && i < 63; ++i) {
-        const uint32_t sm = step_meta[static_cast<size_t>(i)];
-        const bool prop = (sm & 0xffu) == OP_PROP, obs0 = ((sm >> 24) & 1u) != 0u && ((sm >> 25) & 3u) == 0u;
-        const uint32_t rung = (sm >> 27) & 7u;
-        if (prop && obs0 && rung >= 1u && rung <= 4u && (sm >> 31) == 0u) fast |= 1ull << i;
-      }
-      cp->cls_fast_mask.push_back(fast);
-    }
-    // Which members share a chunk is free (any G subjects of the class may share a propagator).  `spread`: member j of
-    // chunk c is the (c + j * n_chunks)-th subject of the class, so the G rows a block writes at one step are far
-    // apart while neighbouring blocks write neighbouring subjects: G slowly advancing write fronts instead of every
-    // block covering its own 8-subject region (tools/experiments/store_pattern_probe.hip, rows B vs H).
-    const size_t n_chunks_cls = (mem.size() + static_cast<size_t>(G) - 1) / static_cast<size_t>(G);
-    std::vector<int32_t> pick(static_cast<size_t>(G));
-    for (size_t c = 0; c < n_chunks_cls; ++c) {
-      int32_t n = 0;
-      for (int32_t j = 0; j < G; ++j) {
-        const size_t idx = spread ? (c + static_cast<size_t>(j) * n_chunks_cls) : (c * static_cast<size_t>(G) + static_cast<size_t>(j));
-        if (idx < mem.size()) pick[static_cast<size_t>(n++)] = mem[idx];
-      }
-      cp->chunk_cls.push_back(out_cls);
-      cp->chunk_n.push_back(n);
-      cp->chunk_val_off.push_back(static_cast<int64_t>(cp->val.size()));
-      for (int32_t j = 0; j < G; ++j) {
-        cp->chunk_subj.push_back(j < n ? pick[static_cast<size_t>(j)] : -1);
-        cp->chunk_row.push_back(j < n ? hp.subj_obs_off[pick[static_cast<size_t>(j)]] : 0);
-      }
-      const size_t base = cp->val.size();
-      cp->val.resize(base + static_cast<size_t>(L) * G, 0.0);
-      cp->dtv.resize(base + static_cast<size_t>(L) * G, 0.0);
-      if (dyn) {
-        cp->facp.resize((base + static_cast<size_t>(L) * G) * nfac, 1.0);
-        cp->faco.resize((base + static_cast<size_t>(L) * G) * nfac, 1.0);
-      }
-      for (int32_t j = 0; j < n; ++j) {
-        const int64_t s0 = os.subj_op_off[pick[static_cast<size_t>(j)]];
-        for (int64_t i = 0; i < r1 - r0; ++i) {
-          const int32_t st = step_of_op[static_cast<size_t>(i)];
-          if (dyn) {  // this member's covariate factors at the op: the PROP's rate constants, the observation's volume
-            const int32_t so = obs_step_of_op[static_cast<size_t>(i)];
-            const double* src = &os.op_fac[static_cast<size_t>(s0 + i) * nfac];
-            if (so >= 0)
-              std::memcpy(&cp->faco[(base + static_cast<size_t>(so) * G + j) * nfac], src, nfac * sizeof(double));
-            else if (st >= 0 && (os.op_meta[s0 + i] & 0xffu) == OP_PROP)
-              std::memcpy(&cp->facp[(base + static_cast<size_t>(st) * G + j) * nfac], src, nfac * sizeof(double));
-          }
-          if (st < 0) continue;
-          const uint32_t kind = os.op_meta[s0 + i] & 0xffu;
-          double v = 0.0;
-          if (kind == OP_BOLUS) v = os.op_a[s0 + i];
-          if (kind == OP_PROP) v = os.op_b[s0 + i];
-          if (kind == OP_RESET && lagged) v = os.op_a[s0 + i];  // this member's occasion: where its lagged boluses are listed
-          cp->val[base + static_cast<size_t>(st) * G + j] = v;
-          if (loose && kind == OP_PROP) cp->dtv[base + static_cast<size_t>(st) * G + j] = os.op_a[s0 + i];
-        }
-      }
-      {
-        uint64_t mask = 0;
-        for (int64_t st = 0; st < L; ++st) {
-          bool any = false;
-          for (int32_t j = 0; j < n; ++j) any |= cp->val[base + static_cast<size_t>(st) * G + j] != 0.0;
-          if (any) mask |= 1ull << (st < 63 ? st : 63);
-        }
-        if (L > 63) mask |= 1ull << 63;  // (steps past the mask's width always fetch their values)
-        cp->chunk_rate_mask.push_back(mask);
-      }
-      cp->n_classed_subjects += n;
-    }
-    ++out_cls;
-  };
-  std::vector<int32_t> leftover;  // members of classes too small to batch: second chance as loose classes
-  for (size_t c = 0; c < members.size(); ++c) {
-    if (dyn || static_cast<int32_t>(members[c].size()) < min_class_size) {
-      leftover.insert(leftover.end(), members[c].begin(), members[c].end());
-      continue;
-    }
-    emit_class(members[c], cls_rep[c], false);
-  }
-  cp->n_chunks_exact = static_cast<int64_t>(cp->chunk_cls.size());
-  if (loose_classes && !leftover.empty()) {
-    std::sort(leftover.begin(), leftover.end());
-    constexpr uint32_t kShape = 0x00ffffffu;  // kind | io: what a loose class shares (ladder bits and lengths are free)
-    auto same_shape = [&](int64_t x, int64_t y) {
-      const int64_t x0 = os.subj_op_off[x], x1 = os.subj_op_off[x + 1];
-      const int64_t y0 = os.subj_op_off[y], y1 = os.subj_op_off[y + 1];
-      if (x1 - x0 != y1 - y0) return false;
-      for (int64_t i = 0; i < x1 - x0; ++i)
-        if ((os.op_meta[x0 + i] & kShape) != (os.op_meta[y0 + i] & kShape)) return false;
-      return true;
-    };
-    std::unordered_map<uint64_t, std::vector<int32_t>> lbuckets;
-    std::vector<int32_t> lrep;
-    std::vector<std::vector<int32_t>> lmembers;
-    for (int32_t s : leftover) {
-      const int64_t o0 = os.subj_op_off[s], o1 = os.subj_op_off[s + 1];
-      uint64_t h = static_cast<uint64_t>(o1 - o0);
-      for (int64_t o = o0; o < o1; ++o) h = mix64(h, static_cast<uint64_t>(os.op_meta[o] & kShape));
-      auto& ids = lbuckets[h];
-      int32_t cls = -1;
-      for (int32_t c : ids)
-        if (same_shape(lrep[c], s)) {
-          cls = c;
-          break;
-        }
-      if (cls < 0) {
-        cls = static_cast<int32_t>(lrep.size());
-        lrep.push_back(s);
-        lmembers.emplace_back();
-        ids.push_back(cls);
-      }
-      lmembers[cls].push_back(s);
-    }
-    // a loose chunk does G members' arithmetic whatever it holds (no propagator to share): below ~3/4 full the
-    // generic walker is the cheaper way to serve its subjects
-    const int32_t min_loose = std::max(min_class_size, (3 * G + 3) / 4);
-    for (size_t c = 0; c < lmembers.size(); ++c) {
-      if (static_cast<int32_t>(lmembers[c].size()) < min_loose)
-        cp->generic_subjects.insert(cp->generic_subjects.end(), lmembers[c].begin(), lmembers[c].end());
-      else
-        emit_class(lmembers[c], lrep[c], true);
-    }
-  } else {
-    cp->generic_subjects.insert(cp->generic_subjects.end(), leftover.begin(), leftover.end());
-  }
-  cp->n_chunks = static_cast<int64_t>(cp->chunk_cls.size());
-  cp->chunk_val_off.push_back(static_cast<int64_t>(cp->val.size()));  // sentinel: chunk c's block is [off[c], off[c+1])
-  std::sort(cp->generic_subjects.begin(), cp->generic_subjects.end());
-}
-
-namespace {
-
-// packed per-op records (pmx_devtypes.hpp DevOps::op_rec)
-void pack_op_rec(const OpStream& os, const CompileKey& key, std::vector<double>* out) {
-  const bool times = !os.op_t0.empty();
-  if (key.eq_kind == PMX_EQ_ODE) {
-    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 6, 0.0);
-    for (int64_t o = 0; o < os.n_ops; ++o) {
-      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]) | (static_cast<uint64_t>(static_cast<uint32_t>(os.op_n[o])) << 32);
-      std::memcpy(&rec[6 * o], &w, 8);
-      rec[6 * o + 1] = os.op_a[o];
-      rec[6 * o + 2] = os.op_b[o];
-      rec[6 * o + 3] = key.n_rate > 0 ? os.op_rate[o * key.n_rate] : 0.0;
-      rec[6 * o + 4] = times ? os.op_t0[o] : 0.0;
-      rec[6 * o + 5] = times ? os.op_t1[o] : 0.0;
-    }
-    out->swap(rec);
-  } else {  // analytical: {meta (bits), a, b, t0} = 32 bytes
-    std::vector<double> rec(static_cast<size_t>(os.n_ops) * 4, 0.0);
-    for (int64_t o = 0; o < os.n_ops; ++o) {
-      const uint64_t w = static_cast<uint64_t>(os.op_meta[o]);
-      std::memcpy(&rec[4 * o], &w, 8);
-      rec[4 * o + 1] = os.op_a[o];
-      rec[4 * o + 2] = os.op_b[o];
-      rec[4 * o + 3] = times ? os.op_t0[o] : 0.0;
-    }
-    out->swap(rec);
-  }
-}
-
-// one 64-byte record per op for the matrix-free walker (DevOps::op_kfac)
-void pack_op_kfac(const OpStream& os, const CompileKey& key, std::vector<double>* out) {
-  const size_t n_ops = os.op_meta.size();
-  const size_t fw = static_cast<size_t>(key.n_derived) * PMX_MAX_FACTORS;
-  std::vector<double> kf(n_ops * 8, 1.0);
-  for (size_t o = 0; o < n_ops; ++o) {
-    for (int j = 0; j < key.kfac_n && j < 7; ++j) {
-      const int dd = key.kfac_map[j];
-      if (dd < 0 || dd >= key.n_derived) continue;
-      double f = 1.0;  // the parameter's factors multiplied out: theta * (f0 * f1) for the descriptor's (theta * f0) * f1
-      for (int q = 0; q < key.derived[dd].n_factors && q < PMX_MAX_FACTORS; ++q) f *= os.op_fac[o * fw + static_cast<size_t>(dd) * PMX_MAX_FACTORS + q];
-      kf[o * 8 + j] = f;
-    }
-    kf[o * 8 + 7] = os.op_a[o];
-  }
-  out->swap(kf);
-}
-
-// what the log-likelihood kernels read of a class plan besides the plan itself: prog_rec, the per-chunk observation
-// counts and block offsets, and the 64-byte chunk headers
-void pack_class_ll(StreamPlan* sp) {
-  const ClassPlan& cp = sp->cp;
-  std::vector<double> prec((cp.prog_meta.size() + 1) * 2, 0.0);
-  for (size_t i = 0; i < cp.prog_meta.size(); ++i) {
-    const uint64_t w = cp.prog_meta[i];
-    std::memcpy(&prec[2 * i], &w, 8);
-    prec[2 * i + 1] = cp.prog_dt[i];
-  }
-  sp->prog_rec.swap(prec);
-  sp->chunk_nobs.resize(static_cast<size_t>(cp.n_chunks));
-  for (int64_t c = 0; c < cp.n_chunks; ++c) {
-    const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
-    int32_t nobs = 0;
-    for (int64_t o = cp.cls_prog_off[cl]; o < cp.cls_prog_off[cl + 1]; ++o) nobs += (cp.prog_meta[static_cast<size_t>(o)] >> 24) & 1u;
-    sp->chunk_nobs[static_cast<size_t>(c)] = nobs;
-  }
-  std::vector<int64_t>& off = sp->chunk_obs_off;
-  off.resize(static_cast<size_t>(cp.n_chunks) + 1);
-  int64_t at = 0;
-  for (int64_t c = 0; c < cp.n_chunks; ++c) {
-    off[static_cast<size_t>(c)] = at;
-    at += (static_cast<int64_t>(sp->chunk_nobs[static_cast<size_t>(c)]) * 2 + 2) * cp.G;
-  }
-  off[static_cast<size_t>(cp.n_chunks)] = at;  // sentinel
-  sp->cobs_size = at;
-  // one 64-byte record per chunk for pmx_analytical_classed_ll (pmx_kernels.hpp DevClassPlan::chunk_hdr): everything
-  // the kernel needs of a chunk in ONE scalar fetch.  32-bit offsets and 16-bit counts: a plan outside those
-  // limits simply keeps the round-2 kernel (chunk_hdr stays empty).
-  bool fits = cp.G <= 8 && at < (int64_t{1} << 32) && static_cast<int64_t>(cp.val.size()) < (int64_t{1} << 32) &&
-              static_cast<int64_t>(cp.prog_meta.size()) < (int64_t{1} << 32);
-  for (size_t cl = 0; cl + 1 < cp.cls_prog_off.size() && fits; ++cl)
-    fits = cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl] < 65536;
-  if (!fits) return;
-  std::vector<uint32_t> hdr((static_cast<size_t>(cp.n_chunks) + 1) * 16, 0);
-  for (int64_t c = 0; c < cp.n_chunks; ++c) {
-    uint32_t* q = &hdr[static_cast<size_t>(c) * 16];
-    const int32_t cl = cp.chunk_cls[static_cast<size_t>(c)];
-    q[0] = static_cast<uint32_t>(cp.chunk_n[static_cast<size_t>(c)]) |
-           (static_cast<uint32_t>(cp.cls_prog_off[cl + 1] - cp.cls_prog_off[cl]) << 16);
-    q[1] = static_cast<uint32_t>(cp.cls_prog_off[cl]);
-    q[2] = static_cast<uint32_t>(cp.chunk_val_off[static_cast<size_t>(c)]);
-    q[3] = static_cast<uint32_t>(off[static_cast<size_t>(c)]);
-    const uint64_t rm = cp.chunk_rate_mask[static_cast<size_t>(c)], fm = cp.cls_fast_mask[cl];
-    q[4] = static_cast<uint32_t>(rm);
-    q[5] = static_cast<uint32_t>(rm >> 32);
-    q[6] = static_cast<uint32_t>(fm);
-    q[7] = static_cast<uint32_t>(fm >> 32);
-    for (int32_t j = 0; j < cp.G; ++j) q[8 + j] = static_cast<uint32_t>(cp.chunk_subj[static_cast<size_t>(c) * cp.G + j]);
-  }
-  sp->chunk_hdr.swap(hdr);
-}
-
-}  // namespace
-
-int32_t plan_stream(const HostPopulation& hp, const CompileKey& key, const ClassTunables& ct, StreamPlan* sp, std::string* err) {
-  OpStream& os = sp->os;
-  const int32_t rc = compile_ops(hp, key, &os, err);
-  if (rc != PMX_OK) return rc;
-  pack_op_rec(os, key, &sp->op_rec);
-  if (key.kfac_n > 0 && !os.op_fac.empty()) pack_op_kfac(os, key, &sp->op_kfac);
-  sp->no_rates = true;  // (analytical streams: a PROP's op_b is its rate)
-  for (size_t o = 0; o < os.op_meta.size() && sp->no_rates; ++o)
-    if ((os.op_meta[o] & 0xffu) == OP_PROP && os.op_b[o] != 0.0) sp->no_rates = false;
-  sp->eig_reuse = false;  // (covariate streams: bit 27 of a PROP = "same rate constants as the previous built segment")
-  if (key.prop_cache_slots > 0 && !os.op_fac.empty())
-    for (size_t o = 0; o < os.op_meta.size() && !sp->eig_reuse; ++o)
-      if ((os.op_meta[o] & 0xffu) == OP_PROP && (os.op_meta[o] & (1u << 27))) sp->eig_reuse = true;
-  sp->prop_reuse_fraction = os.n_prop > 0 ? static_cast<double>(os.n_prop_reused) / static_cast<double>(os.n_prop) : 0.0;
-  if (key.eq_kind == PMX_EQ_ANALYTICAL && !key.user_cov && key.lag_mask == 0 && os.op_fac.empty())
-    build_step_stream(os, &sp->subj_step_off, &sp->step_rec);
-  if (key.class_g > 0) {
-    const int32_t min_class = ct.min_class > 0 ? ct.min_class : key.class_g / 2;
-    const bool spread = ct.spread < 0 ? true : ct.spread != 0;  // (0.94-0.97 vs 1.05-1.11 ms on C3 in most allocations, never slower: tools/experiments/alloc_tune.py)
-    const bool loose = ct.loose < 0 ? true : ct.loose != 0;  // subjects without a shared design still share a program shape: batched with per-member step lengths
-    build_class_plan(hp, os, key.class_g, min_class, &sp->cp, key.ladder, spread, loose);
-    if (sp->cp.n_chunks > 0) pack_class_ll(sp);
-  }
+  order_subjects(hp.n_subjects, os);
   return PMX_OK;
 }
 

@@ -27,8 +27,7 @@ namespace pmx {
 
 // enum OpKind { OP_RESET, OP_BOLUS, OP_OBS, OP_PROP }: pmx_devtypes.hpp
 
-// op_meta layout: bits 0..7 kind, 8..23 io (input / outeq / reset: 1 = run init), 24..31 unused
-inline uint32_t make_meta(uint32_t kind, uint32_t io) { return kind | (io << 8); }
+// op_meta layout (kind, io and the flags in bits 24..31), make_meta: the op-word table in pmx_devtypes.hpp
 
 // Sorted, validated copy of the caller's events (model independent).
 struct HostPopulation {
@@ -77,18 +76,18 @@ struct CompileKey {
   // user (hiprtc) analytical models, pmx_analytical.hpp:
   bool lag_merge = false;   // every input of lag_mask shares ONE list per occasion (lagb_input says which); the lane
                             // sorts it by its own landing times (a user lag may differ from bolus to bolus)
-  bool solve_marks = false; // bit 24 of a PROP op = it continues the previous PROP's solve (seq_eq's parameter vector
+  bool solve_marks = false; // Continues on a PROP op = it continues the previous PROP's solve (seq_eq's parameter vector
                             // lives for one solve, analytical/mod.rs:331)
   bool full_rates = false;  // analytical: op_rate carries rateiv of EVERY input (a user `eq` may read any of them)
   bool user_cov = false;    // covariates are looked up on the device (segment tables uploaded; no op_cov / op_fac)
   int32_t prop_cache_slots = 0;  // covariate-derived rate constants: PROP ops of one occasion with the same (length,
-                                 // covariate factors) have the same propagator; bits 24-26 of such ops say
-                                 // "compute and keep in slot k" / "take slot k" (prop_cache_codes, pmx_compile.cpp)
+                                 // covariate factors) have the same propagator; the Cache code of such ops says
+                                 // "compute and keep in slot k" / "take slot k" (code_prop_cache, pmx_compile.cpp)
   // three-compartment covariate models: op_kfac rows (DevOps) are built for this kernel-parameter -> derived-value map
   int32_t kfac_n = 0;                 // kernel parameters (0 = no op_kfac)
   int8_t kfac_map[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // derived index behind kernel parameter j, -1 = a primary parameter
   bool ladder = false;     // analytical, theta-only coefficients, no lag: PROP ops carry the exponential-ladder code
-                           // (bits 27-29 of op_meta, pmx_structures.hpp ladder_pow)
+                           // (Rung of op_meta, pmx_structures.hpp ladder_pow)
   bool operator==(const CompileKey& o) const {
     return eq_kind == o.eq_kind && cov_time_mode == o.cov_time_mode && rk4_h_max == o.rk4_h_max &&
            n_rate == o.n_rate && rate_input == o.rate_input && class_g == o.class_g && lag_mask == o.lag_mask &&
@@ -103,7 +102,7 @@ struct OpStream {
   CompileKey key;
   int64_t n_ops = 0;
   std::vector<int64_t> subj_op_off;  // [S+1]
-  std::vector<uint32_t> op_meta;     // kind | io<<8
+  std::vector<uint32_t> op_meta;     // the op word (pmx_devtypes.hpp)
   std::vector<double> op_a;          // BOLUS amount | OBS t_obs | PROP dt
   std::vector<double> op_b;          // PROP: rateiv[0] (analytical) / h (ODE)
   std::vector<int32_t> op_n;         // ODE PROP: RK4 step count (empty for analytical)
@@ -140,7 +139,7 @@ struct ClassPlan {
   int32_t G = 0;                       // members per chunk (register batch of the classed kernel)
   int64_t n_chunks = 0;
   int64_t n_classed_subjects = 0;
-  std::vector<uint32_t> prog_meta;     // concatenated class programs: kind | io<<8 | obs_after<<24 | outeq<<25
+  std::vector<uint32_t> prog_meta;     // concatenated class programs: Kind | Io | ObsAfter | Out | Rung | Flush (pmx_devtypes.hpp)
   std::vector<double> prog_dt;         // PROP: dt
   // lag models (one lagged input; exact classes only): the absolute [t0, t1) of every PROP step and, on a RESET step,
   // the time of the occasion's first event that stays in the list - what a lane compares its lagged bolus times with
@@ -183,7 +182,7 @@ void build_class_plan(const HostPopulation& hp, const OpStream& os, int32_t G, i
                       bool ladder = true, bool spread = false, bool loose_classes = false);
 
 // Fused per-subject step programs for the lean generic walker (pmx_kernels.hpp DevSteps): every OBS op rides on the step
-// in front of it (bit 24 + outeq in bits 25-26, like the class plan's programs); an observation with nothing in front of
+// in front of it (ObsAfter + Out, like the class plan's programs); an observation with nothing in front of
 // it in its subject, or a second one at the same instant, is a step of kind OP_OBS.  rec = [n_steps + 1][4] doubles
 // {meta bits, a, b, 0} (the last record is padding).  Analytical streams without lag only.
 void build_step_stream(const OpStream& os, std::vector<int64_t>* subj_step_off, std::vector<double>* rec);
@@ -219,7 +218,7 @@ struct StreamPlan {
   int64_t cobs_size = 0;
   std::vector<uint32_t> chunk_hdr;      // DevClassPlan::chunk_hdr, [n_chunks + 1][16]; empty: the plan does not fit
   bool no_rates = false;                // no PROP of the stream has an active infusion
-  bool eig_reuse = false;               // some PROP repeats the previous built segment's covariate factor row (bit 27)
+  bool eig_reuse = false;               // some PROP repeats the previous built segment's covariate factor row (SameFac)
   double prop_reuse_fraction = 0.0;     // share of PROP ops that take a kept propagator
 };
 int32_t plan_stream(const HostPopulation& hp, const CompileKey& key, const ClassTunables& ct, StreamPlan* out, std::string* err);

@@ -14,6 +14,51 @@ namespace pmx {
 // op kinds of the flattened per-subject stream (pmx_compile.hpp OpStream)
 enum OpKind : uint32_t { OP_RESET = 0, OP_BOLUS = 1, OP_OBS = 2, OP_PROP = 3 };
 
+// The op word: 32 bits of an op (OpStream::op_meta, the low half of an op_rec word), of a step record (DevSteps::rec)
+// and of a class-program step (ClassPlan::prog_meta, prog_rec).  The host compiler (pmx_compile.cpp, pmx_plan.cpp)
+// writes it, the kernels decode it; the names below are the only place the bit numbers live.
+//
+//  bits   name          on            in records        written when                     meaning
+//  0-7    Kind          every op      ops, steps, progs always                           OpKind
+//  8-23   Io            every op      ops, steps, progs always                           BOLUS input | OBS outeq | RESET 1 = run init
+//  24-26  Cache         PROP          ops               key.prop_cache_slots > 0 and the 0 build | 1+k build, keep in slot k |
+//                                                       stream carries op_fac            1+slots+k take slot k
+//  24     Continues     PROP          ops               key.solve_marks                  a later sub-segment of the same solve
+//  24     ObsAfter      any step      steps, progs      an OBS op follows the step       emit a prediction row after the step
+//  25-26  Out           any step      steps, progs      with ObsAfter                    that observation's outeq (& 3)
+//  25-26  First         RESET         ops               the stream has lag slots         PMX_EV_* kind of the occasion's first
+//                                                                                        event that stays in the list, 3 = none
+//  27-29  Rung          PROP          ops, steps, progs key.ladder (ops, steps); the     n in 1..4: dt = n x the previous PROP's
+//                                                       plan's ladder, exact classes     (ladder_code), 0 = fresh exponentials
+//  27     SameFac       PROP          ops               like Cache                       same covariate factor row as the occasion's
+//                                                                                        previous built PROP
+//  31     Flush         OBS;          ops, progs        the stream has lag slots, no     take the lagged boluses landing before the
+//                       the step it                     PROP precedes the observation    observation's time first
+//                       is fused into
+//
+// Fields that share bits never meet:
+//  - Cache / Continues: the cache pass needs op_fac, which a user_cov stream does not carry; only user models
+//    (user_cov) set solve_marks.
+//  - Rung / SameFac: ladder is for theta-only rate constants, SameFac for covariate-derived ones (key_for: ladder = !dyn).
+//  - Cache, Continues, SameFac, First / ObsAfter, Out: the first four exist in the op stream only, the last two in step and
+//    program records only - those are built from Kind and Io afresh; of the flags, steps copy Rung and programs Flush.
+//  - First / everything else in bits 24-26: First is on RESET ops, the others on PROP ops.
+//  - Flush shares with nobody (Rung ends at bit 29).
+constexpr uint32_t kOpKindMask = 0xffu;
+constexpr uint32_t kOpIoShift = 8, kOpIoMask = 0xffffu;
+constexpr uint32_t kOpCacheShift = 24, kOpCacheMask = 7u;
+constexpr uint32_t kOpContinuesShift = 24;
+constexpr uint32_t kOpObsAfterShift = 24;
+constexpr uint32_t kOpOutShift = 25, kOpOutMask = 3u;
+constexpr uint32_t kOpFirstShift = 25, kOpFirstMask = 3u;
+constexpr uint32_t kOpRungShift = 27, kOpRungMask = 7u;
+constexpr uint32_t kOpSameFacBit = 1u << 27;
+constexpr uint32_t kOpFlushShift = 31;
+
+constexpr uint32_t make_meta(uint32_t kind, uint32_t io) { return kind | (io << kOpIoShift); }
+constexpr uint32_t op_kind(uint32_t meta) { return meta & kOpKindMask; }
+constexpr uint32_t op_io(uint32_t meta) { return (meta >> kOpIoShift) & kOpIoMask; }
+
 // Model description as the kernels see it (passed by value in the kernarg segment).
 struct DevModel {
   int32_t eq_kind, kernel;
@@ -42,7 +87,7 @@ struct DevModel {
 };
 constexpr int kMaxLagSlots = 4;
 // closure walkers (pmx_userlag.hpp): lagged boluses of one occasion whose landing times a lane keeps sorted in a private
-// array; an occasion with more takes the model's PMX_USER_BIG_LISTS build (compiled on demand, pmx_api.cpp)
+// array; an occasion with more takes the model's PMX_USER_BIG_LISTS build (compiled on demand, pmx_launch.cpp)
 #ifndef PMX_USER_LAG_KEPT
 #define PMX_USER_LAG_KEPT 64
 #endif

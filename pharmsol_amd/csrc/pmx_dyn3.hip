@@ -114,8 +114,8 @@ __global__ __launch_bounds__(kBlock, PMX_DYN3_WAVES) void pmx_analytical_dyn3(De
         rec_n = sload_here<u32x16>(ops.op_kfac + on * 8);
         __builtin_amdgcn_sched_barrier(0);
       }
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       auto rec_f64 = [&rec](int k) {
         return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(rec[2 * k + 1]) << 32) | rec[2 * k]));
       };
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kBlock, PMX_DYN3_WAVES) void pmx_analytical_dyn3(De
       const double* cov = ops.op_fac + o * (m.n_derived * PMX_MAX_FACTORS);  // (derived volumes: lane_out)
       if (kind == OP_PROP) {
         // bits 24-26: 0 = build; 1 + k = build and keep in slot k; 1 + S + k = take slot k (pmx_compile.cpp)
-        const uint32_t rc = (meta >> 24) & 7u;
+        const uint32_t rc = (meta >> kOpCacheShift) & kOpCacheMask;
         const uint32_t n_slots = static_cast<uint32_t>(prop_slots);
         double q[LM::NKP], keep[ND0];
         {
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock, PMX_DYN3_WAVES) void pmx_analytical_dyn3(De
           // bit 27: same covariate factor row as the occasion's previous built segment - its eigenvalues still hold
           bool ok;
           if constexpr (EIGR) {
-            ok = (meta & (1u << 27)) ? LM::S::template direct0_make<true>(q, a, keep, lprev, okprev)
+            ok = (meta & kOpSameFacBit) ? LM::S::template direct0_make<true>(q, a, keep, lprev, okprev)
                                      : LM::S::template direct0_make<false>(q, a, keep, lprev, okprev);
           } else {
             ok = LM::S::template direct0_make<false>(q, a, keep, lprev, okprev);

@@ -90,8 +90,8 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
     }
     for (int64_t o = o0; o < o1; ++o) {
       const uint32_t meta = c_op_meta[o];
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       const double a = c_op_a[o];
       const double* cov = ops.op_fac + o * (m.n_derived * PMX_MAX_FACTORS);  // this op's covariate factors
       if (kind == OP_PROP) {
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
         } else if constexpr (DYN) {
           // bits 24-26: 0 = build; 1 + k = build and keep in slot k; 1 + S + k = take slot k (same length, same
           // covariate factors earlier in this occasion: the same transition matrix).  Wave-uniform: scalar branches.
-          const uint32_t rc = (meta >> 24) & 7u;
+          const uint32_t rc = (meta >> kOpCacheShift) & kOpCacheMask;
           const uint32_t n_slots = static_cast<uint32_t>(prop_slots);
           typename LM::S::Prop pr;
           if (rc > n_slots) {  // (kept by a segment of the same kind: with a rate -> F and J, without -> F only)
@@ -124,8 +124,8 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
           if (r != 0.0) LM::S::apply(pr, x, r);
           else LM::S::apply0(pr, x);
         } else {
-          // exponential ladder (pmx_compile.cpp ladder_code): bits 27-29 relate this PROP's length to the previous one's
-          const uint32_t rung = (meta >> 27) & 7u;
+          // exponential ladder (pmx_plan.cpp ladder_code): bits 27-29 relate this PROP's length to the previous one's
+          const uint32_t rung = (meta >> kOpRungShift) & kOpRungMask;
           if (rung == 0u) {
             LM::S::exps(L.coef, a, ex);
           } else if (rung != 1u) {
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
         xpad = 0.0;  // pm_* wrappers re-pad slot 0 with 0 after every kernel call (analytical/mod.rs:70-75)
       } else if (kind == OP_OBS) {
         if constexpr (LAG) {  // no PROP step in front of this observation: lagged boluses may land before it (bit 31)
-          if (meta >> 31) lag_flush_before<NS>(m, ops, ls, a, th, x);
+          if (meta >> kOpFlushShift) lag_flush_before<NS>(m, ops, ls, a, th, x);
         }
         double y = lane_out<KID>(m, L, x, xpad, io, cov);
         if (st == PMX_PAIR_COMPLEX_ROOTS || st == PMX_PAIR_BAD_LAG) y = nanv;

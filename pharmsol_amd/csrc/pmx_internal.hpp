@@ -1,7 +1,7 @@
 // pmx_internal.hpp — what the translation units of the C ABI share: the opaque handles of include/pmx.h, the device
 // stream of a (population, model flavour) pair and the developer switches.
 //   pmx_api.cpp     C entry points, model creation and checks, host-pointer workspace, debug views
-//   pmx_stream.cpp  DeviceStream: plan (pmx_compile.cpp plan_stream), upload, log-likelihood slots
+//   pmx_stream.cpp  DeviceStream: plan (pmx_plan.cpp plan_stream), upload, log-likelihood slots
 //   pmx_launch.cpp  compile key, route decision, enqueue
 #pragma once
 

@@ -51,7 +51,7 @@ struct DevClassPlan {
 
 // Fused per-subject step programs for the lean generic walker (pmx_analytical_steps): what the class plan builds per
 // CLASS, built per SUBJECT - every OBS op folded into the step in front of it, one packed 32-byte record per step
-// {meta (u64 bits: kind | io << 8 | obs-after << 24 | outeq << 25 | ladder rung << 27), a, b, 0}, one record of padding
+// {meta (u64 bits: Kind | Io | ObsAfter | Out | Rung of the op word, pmx_devtypes.hpp), a, b, 0}, one record of padding
 // behind the last step (the walker requests step o + 1 while it works on step o).
 struct DevSteps {
   const int64_t* subj_step_off;  // [S+1]

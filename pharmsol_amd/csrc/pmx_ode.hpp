@@ -1,6 +1,6 @@
 // pmx_ode.hpp — the ODE back-end's device code, generic over a model policy: fixed-step classic RK4 per constant-
 // rate piece, the GRID and PAIR walkers (ode/mod.rs:609-823 semantics).  Included by
-// pmx_kernels.hip with the built-in diffeq bodies and by the source hiprtc compiles for a user model (pmx_jit.cpp).
+// pmx_ode_builtin.hip with the built-in diffeq bodies and by the source hiprtc compiles for a user model (pmx_jit.cpp).
 #pragma once
 
 #include "pmx_device.hpp"
@@ -544,8 +544,8 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
     double clk = 0.0;  // LAG: the lane's solver clock (see ode_lag_open_occasion)
     for (int64_t o = o0; o < o1; ++o) {
       const uint32_t meta = uniform32(as_const(ops.op_meta)[o]);
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       const double a = uniformf64(as_const(ops.op_a)[o]);
       if (kind == OP_PROP) {
         double rs[M::NR];
@@ -595,7 +595,7 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
         ode_reset<M>(L, io, x);
         if constexpr (LAG)
           clk = ode_lag_open_occasion<M, SOLV>(m, ops, ls, static_cast<int64_t>(a), uniformf64(as_const(ops.op_t0)[o]),
-                                                (meta >> 25) & 3u, uniformf64(as_const(ops.op_b)[o]), L, th, x, as);
+                                                (meta >> kOpFirstShift) & kOpFirstMask, uniformf64(as_const(ops.op_b)[o]), L, th, x, as);
       }
     }
     if constexpr (LL) {
@@ -775,8 +775,8 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
           op_t0 = rec2.x;
           op_t1 = rec2.y;
         }
-        const uint32_t kind = meta & 0xffu;
-        const int io = static_cast<int>((meta >> 8) & 0xffffu);
+        const uint32_t kind = meta & kOpKindMask;
+        const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
         bool next_op = true;  // LAG: a PROP / an occasion opening stays the current op until the branch above closes it
         if (kind == OP_PROP) {
           ode_rates<M>(m, ops.op_rate, o, ops.n_rate, op_r0, rs);
@@ -834,7 +834,7 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
             int which;
             const double tau = lag_next(m, ops, ls, which);
             const double t_first = op_t0;
-            if ((tau < t_first || (tau == t_first && lag_lands_first(ls, which, (meta >> 25) & 3u))) && t_first < inf) {
+            if ((tau < t_first || (tau == t_first && lag_lands_first(ls, which, (meta >> kOpFirstShift) & kOpFirstMask))) && t_first < inf) {
               lag_apply_bolus<NS>(m, ops, ls, which, th, x);
   #pragma unroll
               for (int j = 0; j < M::NR; ++j) rs[j] = 0.0;
@@ -854,7 +854,7 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
       // of dx/dt = -ke x + r (tools/experiments/rk4_latency_probe.hip: 46 ns/step for a lone wave, 333 ns/trip here), and a
       // batch of a few 10k pairs is one wave per SIMD, i.e. latency-bound.  Bounded, so a lane that needs its next
       // op waits for at most that many steps of its neighbours, not for the longest piece in the wave; the host
-      // picks the bound from the batch size (pmx_api.cpp).
+      // picks the bound from the batch size (pmx_launch.cpp).
       const int32_t spt = ops.steps_per_trip;
       if constexpr (ADAPT) {
         for (int32_t j = 0; j < spt && stepping; ++j) stepping = dopri5_advance<M>(m, L, x, rs, t_run, t_run_end, as);

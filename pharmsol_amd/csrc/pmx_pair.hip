@@ -66,8 +66,8 @@ __global__ __launch_bounds__(kBlock) void pmx_analytical_pair(DevModel m, DevOps
       o = og + j;
       if (o >= o1) break;
       const uint32_t meta = static_cast<uint32_t>(__double_as_longlong(q.x));
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       const double a = q.y;
       const double* cov = ops.op_fac + o * (m.n_derived * PMX_MAX_FACTORS);  // this op's covariate factors
       if (kind == OP_PROP) {
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void pmx_analytical_pair(DevModel m, DevOps
         xpad = 0.0;
       } else if (kind == OP_OBS) {
         if constexpr (LAG) {  // (see the GRID kernel)
-          if (meta >> 31) lag_flush_before<NS>(m, ops, ls, a, th, x);
+          if (meta >> kOpFlushShift) lag_flush_before<NS>(m, ops, ls, a, th, x);
         }
         double y = lane_out<KID>(m, L, x, xpad, io, cov);
         if (st == PMX_PAIR_COMPLEX_ROOTS || st == PMX_PAIR_BAD_LAG) y = nanv;

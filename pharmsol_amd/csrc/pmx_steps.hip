@@ -73,12 +73,12 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
       a_n = recp[1];
       b_n = recp[2];
       const uint32_t meta = static_cast<uint32_t>(w);
-      const uint32_t kind = meta & 0xffu;
-      const int io = static_cast<int>((meta >> 8) & 0xffffu);
+      const uint32_t kind = meta & kOpKindMask;
+      const int io = static_cast<int>((meta >> kOpIoShift) & kOpIoMask);
       const double a = __longlong_as_double(static_cast<int64_t>(ab));
       if (kind == OP_PROP) {
         const double r = __longlong_as_double(static_cast<int64_t>(bb));
-        const uint32_t rung = (meta >> 27) & 7u;
+        const uint32_t rung = (meta >> kOpRungShift) & kOpRungMask;
         if (rung == 0u) {
           LM::S::exps(L.coef, a, ex);
         } else if (rung != 1u) {
@@ -94,8 +94,8 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
 #pragma unroll
         for (int i = 0; i < NS; ++i) x[i] = io ? L.xinit[i] : 0.0;
       }  // (OP_OBS: an observation with no step to ride on - the first op of nothing, or a second one at the same instant)
-      if ((meta >> 24) & 1u) {
-        const int oq = static_cast<int>((meta >> 25) & 3u);
+      if ((meta >> kOpObsAfterShift) & 1u) {
+        const int oq = static_cast<int>((meta >> kOpOutShift) & kOpOutMask);
         int out_state = out_state0;
         double inv_vol = inv_vol0;
         if (oq != 0) {  // outputs beyond the first: rare (see pmx_analytical_classed)

@@ -1010,7 +1010,7 @@ __device__ __forceinline__ void make_prop(const typename Structure<ST>::Coef& c,
 // The exponential ladder: when a step's length is n x the previous step's (n = 2, 3, 4; sampling designs on
 // 0.5/1/2/4/8/12/24 h grids are exactly that), pmx_exp(-lambda n dt) = pmx_exp(-lambda dt)^n costs n-1 multiplies instead of
 // an pmx_exp() call.  Each rung multiplies the relative error of the previous one by n; the host caps the
-// cumulative factor (pmx_compile.cpp ladder_codes), which keeps the deviation from a fresh pmx_exp() below 1e-12.
+// cumulative factor (pmx_plan.cpp ladder_code), which keeps the deviation from a fresh pmx_exp() below 1e-12.
 template <int NE>
 __device__ __forceinline__ void ladder_pow(double (&e)[NE], uint32_t n) {
 #pragma unroll

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void pmx_ll_prepare_chunks(LLPrepareArgs a) {
       const int32_t cl = a.chunk_cls[ch];
       int32_t k = 0;
       for (int64_t o = a.cls_prog_off[cl], s = 0; o < a.cls_prog_off[cl + 1]; ++o, ++s) {
-        if ((a.prog_meta[o] >> 24) & 1u) {
+        if ((a.prog_meta[o] >> kOpObsAfterShift) & 1u) {
           if (s < 63 && k < 63 && ((plain >> k) & 1ull)) plain_step |= 1ull << s;
           ++k;
         }
