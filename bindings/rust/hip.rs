@@ -406,6 +406,15 @@ impl HipOde {
         desc.ode_atol = atol;
         Self::from_desc(desc)
     }
+    /// `from_desc` with the auto solver ("LSODA-style"): DOPRI5 with Hairer's stiffness test after every accepted step; a
+    /// lane found stiff steps with ROS2 until its step is back inside DOPRI5's stability interval.  One choice for a
+    /// support grid that holds stiff and non-stiff points; a lane that never switches walks what DOPRI5 walks.
+    pub fn from_desc_auto(mut desc: pmx_model_desc, rtol: f64, atol: f64) -> Result<Self, PharmsolError> {
+        desc.ode_solver = PMX_SOLVER_AUTO;
+        desc.ode_rtol = rtol;
+        desc.ode_atol = atol;
+        Self::from_desc(desc)
+    }
     /// Did the checked solver refuse this pair?  (`status` as `estimate_predictions_matrix` returns it.)
     pub fn step_too_coarse(status: u8) -> bool {
         status as i32 == PMX_PAIR_STEP_TOO_COARSE

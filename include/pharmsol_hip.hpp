@@ -594,7 +594,9 @@ class ODE : public Equation {
   /// explicit) | PMX_SOLVER_ROS2 (adaptive, L-stable: the stiff option, the role of OdeSolver::Bdf / Sdirk) |
   /// PMX_SOLVER_RK4_CHECKED (the fixed-step walk with a step-doubling probe per integration piece, judged against
   /// with_tolerances: a support point whose rates the step does not resolve fails with PMX_PAIR_STEP_TOO_COARSE and
-  /// NaN rows instead of finite nonsense; shorten with_step, or take an adaptive solver).
+  /// NaN rows instead of finite nonsense; shorten with_step, or take an adaptive solver) | PMX_SOLVER_AUTO (DOPRI5 that
+  /// detects stiffness per lane, moves a stiff lane to ROS2 steps and back; a lane that never switches walks what
+  /// PMX_SOLVER_DOPRI5 walks; step counts per pair: pmx_predict_stats_device).
   ODE& with_solver(int32_t solver) { desc_.ode_solver = solver; invalidate(); return *this; }
   ODE& with_tolerances(double rtol, double atol) { desc_.ode_rtol = rtol; desc_.ode_atol = atol; invalidate(); return *this; }
   ODE& with_step(double h_max) { desc_.rk4_h_max = h_max; invalidate(); return *this; }

@@ -233,7 +233,12 @@ typedef struct pmx_model_desc {
    * integration piece (a PROP, or a sub-piece cut around a lagged bolus) is also taken as two half steps; Richardson's
    * estimate e = 16/15 (x_half - x_full) of that step's local error, in the norm above, must be <= 1, else the pair is
    * PMX_PAIR_STEP_TOO_COARSE.  A pair whose probes all pass gets plain RK4's numbers.  8 extra right-hand sides per
-   * piece.  Reads ode_rtol / ode_atol like the adaptive solvers. */
+   * piece.  Reads ode_rtol / ode_atol like the adaptive solvers.
+   * PMX_SOLVER_AUTO = DOPRI5 that detects stiffness per lane and moves that lane to ROS2, and back: the one step
+   * controller of the two methods; after every accepted DOPRI5 step Hairer's test h rho > 3.25 (rho from the two stages
+   * at t + h), 15 such steps in a row switch the lane to ROS2; after every accepted ROS2 step h ||J||_inf <= 1, 6 such
+   * steps in a row switch it back.  A lane that never switches walks exactly what PMX_SOLVER_DOPRI5 walks.  Needs
+   * ode_rtol > 0 and ode_atol > 0.  Per-pair step counts: pmx_predict_stats_device. */
   int32_t ode_solver;
   int32_t reserved_;
   double ode_rtol, ode_atol;
@@ -243,7 +248,10 @@ enum {
   PMX_SOLVER_RK4 = 0,
   PMX_SOLVER_DOPRI5 = 1,
   PMX_SOLVER_ROS2 = 2,        /* stiff: L-stable Rosenbrock, adaptive */
-  PMX_SOLVER_RK4_CHECKED = 3  /* fixed-step RK4 with a step-doubling probe per piece (PMX_PAIR_STEP_TOO_COARSE) */
+  PMX_SOLVER_RK4_CHECKED = 3, /* fixed-step RK4 with a step-doubling probe per piece (PMX_PAIR_STEP_TOO_COARSE) */
+  PMX_SOLVER_AUTO = 5         /* DOPRI5 with per-lane stiffness detection, stiff lanes step with ROS2 ("LSODA-style").  The
+                                 value 4 is no solver and stays refused: tests/test_rk4_checked.py pins it as the invalid
+                                 example. */
 };
 
 typedef struct pmx_population pmx_population; /* opaque */
@@ -384,6 +392,17 @@ int32_t pmx_predict_batch(const pmx_model* model, const pmx_population* pop, con
                           uint8_t* status);
 int32_t pmx_predict_batch_device(const pmx_model* model, const pmx_population* pop, const double* d_theta,
                                  double* d_pred, uint8_t* d_status, void* stream);
+
+/* Per-pair solver statistics of a PMX_SOLVER_AUTO model (any other model: PMX_ERR_INVALID_ARGUMENT, decided before a
+ * device is touched).  pmx_predict_device / pmx_predict_batch_device plus d_stats, one record of four uint32_t per pair
+ * in the order of the status bytes: {accepted explicit (DOPRI5) steps, accepted implicit (ROS2) steps, rejected
+ * attempts, switches of method}.  The record of subject s and support point p is at d_stats + (s * n_support + p) * 4;
+ * the batch form writes [n_subjects][4].  Every pair writes its record. */
+int32_t pmx_predict_stats_device(const pmx_model* model, const pmx_population* pop, const double* d_theta,
+                                 int64_t n_support, double* d_pred, int64_t ld_pred, uint8_t* d_status, void* stream,
+                                 uint32_t* d_stats);
+int32_t pmx_predict_batch_stats_device(const pmx_model* model, const pmx_population* pop, const double* d_theta,
+                                       double* d_pred, uint8_t* d_status, void* stream, uint32_t* d_stats);
 
 /* ---- fused log-likelihood ----------------------------------------------
  * log_likelihood_matrix(eq, &Data, &theta, &AssayErrorModels, progress) (likelihood/matrix.rs:52-106):

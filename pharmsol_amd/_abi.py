@@ -104,6 +104,7 @@ ODE_MODELS = {
 }
 PMX_ODE_CUSTOM = 100
 PMX_SOLVER_RK4, PMX_SOLVER_DOPRI5, PMX_SOLVER_ROS2, PMX_SOLVER_RK4_CHECKED = 0, 1, 2, 3
+PMX_SOLVER_AUTO = 5  # (4 is no solver)
 PMX_PAIR_SOLVER_FAIL = 4
 PMX_PAIR_STEP_TOO_COARSE = 5
 ODE_STATE_COUNT = {"one_cmt_iv": 1, "one_cmt_oral": 2, "two_cmt_iv": 2, "two_cmt_oral": 3, "three_cmt_iv": 3,

@@ -27,7 +27,8 @@ int ode_nparams(int model) {
 }
 
 bool known_ode_solver(int32_t v) {
-  return v == PMX_SOLVER_RK4 || v == PMX_SOLVER_DOPRI5 || v == PMX_SOLVER_ROS2 || v == PMX_SOLVER_RK4_CHECKED;
+  return v == PMX_SOLVER_RK4 || v == PMX_SOLVER_DOPRI5 || v == PMX_SOLVER_ROS2 || v == PMX_SOLVER_RK4_CHECKED ||
+         v == PMX_SOLVER_AUTO;  // (4 is no solver)
 }
 
 // every pmx_model_create* ends here: the model's device-side description is fixed from now on
@@ -345,6 +346,7 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     sp.has_init = m->has_init;
     sp.ncov = d->n_covariates;
     sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
+    sp.auto_solver = d->ode_solver == PMX_SOLVER_AUTO;
     sp.source = pmx::ode_descriptor_source(*d);
     std::string log;
     m->jit_spec = sp;
@@ -395,6 +397,7 @@ pmx::JitSpec spec_of(const pmx_model_desc* d, const char* source, int32_t has_in
   sp.has_init = has_init != 0;
   sp.ncov = d->n_covariates;
   sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
+  sp.auto_solver = d->ode_solver == PMX_SOLVER_AUTO;
   sp.source = source;
   return sp;
 }
@@ -526,6 +529,7 @@ pmx::JitSpec user_spec_of(const pmx_model_desc* d, const char* source, uint32_t 
   sp.fns = fns;
   sp.desc = *d;
   sp.checked = sp.ode_user && d->ode_solver == PMX_SOLVER_RK4_CHECKED;
+  sp.auto_solver = sp.ode_user && d->ode_solver == PMX_SOLVER_AUTO;
   sp.source = source;
   return sp;
 }
@@ -830,6 +834,37 @@ int32_t pmx_predict_device(const pmx_model* model, const pmx_population* cpop, c
   DeviceGuard g;
   PMX_HIP(g.enter(pop->device));
   return enqueue(model, pop, d_theta, n_support, 0, d_pred, ld_pred, d_status, stream);
+}
+
+// the model of a *_stats_device call integrates with PMX_SOLVER_AUTO (checked before any device is touched)
+static bool stats_model_ok(const pmx_model* model) {
+  return model->d.eq_kind == PMX_EQ_ODE && model->d.ode_solver == PMX_SOLVER_AUTO;
+}
+
+int32_t pmx_predict_stats_device(const pmx_model* model, const pmx_population* cpop, const double* d_theta,
+                                 int64_t n_support, double* d_pred, int64_t ld_pred, uint8_t* d_status, void* stream,
+                                 uint32_t* d_stats) {
+  g_err.clear();
+  if (!model) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!stats_model_ok(model)) return fail(PMX_ERR_INVALID_ARGUMENT, "solver statistics exist for PMX_SOLVER_AUTO models only");
+  if (!cpop || !d_theta || !d_pred || !d_stats) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_support <= 0 || ld_pred < n_support) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0 and ld_pred >= n_support");
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  DeviceGuard g;
+  PMX_HIP(g.enter(pop->device));
+  return enqueue(model, pop, d_theta, n_support, 0, d_pred, ld_pred, d_status, stream, nullptr, -1, d_stats);
+}
+
+int32_t pmx_predict_batch_stats_device(const pmx_model* model, const pmx_population* cpop, const double* d_theta,
+                                       double* d_pred, uint8_t* d_status, void* stream, uint32_t* d_stats) {
+  g_err.clear();
+  if (!model) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!stats_model_ok(model)) return fail(PMX_ERR_INVALID_ARGUMENT, "solver statistics exist for PMX_SOLVER_AUTO models only");
+  if (!cpop || !d_theta || !d_pred || !d_stats) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  DeviceGuard g;
+  PMX_HIP(g.enter(pop->device));
+  return enqueue(model, pop, d_theta, 1, 1, d_pred, 1, d_status, stream, nullptr, -1, d_stats);
 }
 
 int32_t pmx_time_predict_device(const pmx_model* model, const pmx_population* cpop, const double* d_theta,

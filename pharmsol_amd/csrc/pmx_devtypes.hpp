@@ -81,9 +81,12 @@ struct DevModel {
   int32_t out_vol_theta[PMX_MAX_OUT]; // theta index behind each output's volume when it is lane-constant (a primary
                                       // parameter, or a derived value without covariate factors: its base parameter); -1 = none
   double rk4_h_max;                   // ODE + lag: pieces split on the device recompute n = ceil(dt / h_max)
-  double ode_rtol, ode_atol;          // adaptive solvers (PMX_SOLVER_DOPRI5, PMX_SOLVER_ROS2)
+  double ode_rtol, ode_atol;          // adaptive solvers (PMX_SOLVER_DOPRI5, PMX_SOLVER_ROS2, PMX_SOLVER_AUTO)
   int32_t ode_stiff;                  // the adaptive step is ROS2 (PMX_SOLVER_ROS2) instead of DOPRI5
   int32_t pad2_;
+  uint32_t* solver_stats;             // pmx_predict_stats_device: [pairs][4] = {accepted explicit, accepted implicit, rejected,
+                                      // switches}, in the order of the status bytes; null otherwise.  Read by the
+                                      // PMX_SOLVER_AUTO kernels only.
 };
 constexpr int kMaxLagSlots = 4;
 // closure walkers (pmx_userlag.hpp): lagged boluses of one occasion whose landing times a lane keeps sorted in a private

@@ -207,4 +207,5 @@ struct LLRequest {
   const int32_t** d_sigma_err = nullptr;  // out (host form): the slot's invalid-sigma counter
 };
 int32_t enqueue(const pmx_model* model, pmx_population* pop, const double* d_theta, int64_t P, int batch, double* d_pred,
-                int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq = nullptr, int state_override = -1);
+                int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq = nullptr, int state_override = -1,
+                uint32_t* d_stats = nullptr);

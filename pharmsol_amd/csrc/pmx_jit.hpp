@@ -26,6 +26,8 @@ struct JitSpec {
   // ODE models of PMX_SOLVER_RK4_CHECKED: the translation unit holds the checked-RK4 entry points INSTEAD of the
   // fixed-step and adaptive ones (a model's solver is fixed at creation), so every other model compiles what it always did
   bool checked = false;
+  // ... and of PMX_SOLVER_AUTO likewise: the auto entry points instead of the others
+  bool auto_solver = false;
   bool big_lists = false;  // closure walkers: compile the > 64-boluses-per-occasion path in (PMX_USER_BIG_LISTS, pmx_userlag.hpp)
 };
 enum JitKind { JIT_ODE = 0, JIT_ANALYTICAL = 1, JIT_ODE_USER = 2 };
@@ -34,7 +36,7 @@ inline JitKind jit_kind(const JitSpec& s) { return s.analytical ? JIT_ANALYTICAL
 // The translation unit handed to hiprtc (user source + policy + the kernel wrappers: 16 for an ODE model - GRID/PAIR x
 // lag x log-likelihood x solver -, 4 for an analytical one - GRID/PAIR x log-likelihood -, 8 for an ODE model with
 // user lag / fa closures - GRID/PAIR x log-likelihood x solver).  A checked-RK4 model (JitSpec::checked) has the one
-// solver: 8 and 4 wrappers.
+// solver: 8 and 4 wrappers; so has an auto model (JitSpec::auto_solver).
 std::string jit_translation_unit(const JitSpec& spec);
 
 // Source text (pmx_derive) of an ANALYTICAL descriptor's derived values (desc.derived[]: theta * covariate factors), for
@@ -53,10 +55,12 @@ bool jit_compile(const JitSpec& spec, std::vector<char>* code, std::string* log)
 
 struct JitModule {
   hipModule_t module = nullptr;
-  hipFunction_t fn[2][2][2][3] = {};  // [mode: 0 GRID, 1 PAIR][LAG][LL][solver: 0 RK4, 1 adaptive, 2 checked RK4]
+  hipFunction_t fn[2][2][2][4] = {};  // [mode: 0 GRID, 1 PAIR][LAG][LL][solver: 0 RK4, 1 adaptive, 2 checked RK4, 3 auto]
 };
-// Load a compiled code object on the CURRENT device and resolve the kernel entry points (`checked`: JitSpec::checked).
-hipError_t jit_load(const std::vector<char>& code, JitModule* out, JitKind kind = JIT_ODE, bool checked = false);
+// Load a compiled code object on the CURRENT device and resolve the kernel entry points (`checked`: JitSpec::checked,
+// `auto_solver`: JitSpec::auto_solver).
+hipError_t jit_load(const std::vector<char>& code, JitModule* out, JitKind kind = JIT_ODE, bool checked = false,
+                    bool auto_solver = false);
 void jit_unload(JitModule* m);
 
 }  // namespace pmx

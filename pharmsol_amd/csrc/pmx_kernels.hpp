@@ -82,7 +82,7 @@ struct Route {
   bool lag, dyn;    // lagged input / kernel parameters depend on covariates (re-prepare per PROP)
   bool eig_reuse;   // dyn3: the stream marks segments that repeat the previous built segment's rate constants (EIGR)
   bool leftover;    // walkers behind a classed launch: the subjects of cls.generic_subjects instead of 0..S-1
-  int32_t solver;   // ODE: 0 = RK4, 1 = DOPRI5, 2 = ROS2, 3 = checked RK4
+  int32_t solver;   // ODE: 0 = RK4, 1 = DOPRI5, 2 = ROS2, 3 = checked RK4, 4 = auto (PMX_SOLVER_AUTO = 5)
   int64_t n;        // walkers: subjects walked; classed: chunks served
   int32_t s_chunk;  // GRID walkers: subjects walked by one block
   int32_t n_ptiles; // GRID: ceil(P / threads)

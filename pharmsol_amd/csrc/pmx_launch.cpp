@@ -172,9 +172,10 @@ pmx::CompileKey key_for(const pmx_model* m, const Tunables& tun, bool has_infusi
     k.rate_input = 0;
     for (int i = 0; i < PMX_MAX_INPUTS; ++i)
       if (m->d.lag_param[i] >= 0) k.lag_mask |= (1u << i);
-    // absolute piece times: a user body may be non-autonomous; the adaptive solver steps on [t0, t1] itself (checked RK4
-    // walks the fixed-step stream as it is)
-    k.want_times = m->custom || m->d.ode_solver == PMX_SOLVER_DOPRI5 || m->d.ode_solver == PMX_SOLVER_ROS2;
+    // absolute piece times: a user body may be non-autonomous; the adaptive solvers (auto is one: its stream is
+    // dopri5's) step on [t0, t1] themselves (checked RK4 walks the fixed-step stream as it is)
+    k.want_times = m->custom || m->d.ode_solver == PMX_SOLVER_DOPRI5 || m->d.ode_solver == PMX_SOLVER_ROS2 ||
+                   m->d.ode_solver == PMX_SOLVER_AUTO;
   }
   return k;
 }
@@ -244,21 +245,24 @@ static_launch_t static_launcher() {
 
 // THE name of a route: every string pmx_last_kernel_name can return is written here.
 const char* route_name(const Route& r) {
-  static const char* const kSolver[4][2][2] = {
+  static const char* const kSolver[5][2][2] = {
       {{"pmx_ode_rk4_grid", "pmx_ode_rk4_grid<lag>"}, {"pmx_ode_rk4_pair", "pmx_ode_rk4_pair<lag>"}},
       {{"pmx_ode_dopri5_grid", "pmx_ode_dopri5_grid<lag>"}, {"pmx_ode_dopri5_pair", "pmx_ode_dopri5_pair<lag>"}},
       {{"pmx_ode_ros2_grid", "pmx_ode_ros2_grid<lag>"}, {"pmx_ode_ros2_pair", "pmx_ode_ros2_pair<lag>"}},
-      {{"pmx_ode_rk4_checked_grid", "pmx_ode_rk4_checked_grid<lag>"}, {"pmx_ode_rk4_checked_pair", "pmx_ode_rk4_checked_pair<lag>"}}};
-  static const char* const kJit[4][2][2] = {
+      {{"pmx_ode_rk4_checked_grid", "pmx_ode_rk4_checked_grid<lag>"}, {"pmx_ode_rk4_checked_pair", "pmx_ode_rk4_checked_pair<lag>"}},
+      {{"pmx_ode_auto_grid", "pmx_ode_auto_grid<lag>"}, {"pmx_ode_auto_pair", "pmx_ode_auto_pair<lag>"}}};
+  static const char* const kJit[5][2][2] = {
       {{"pmx_jit_ode_rk4_grid", "pmx_jit_ode_rk4_grid<lag>"}, {"pmx_jit_ode_rk4_pair", "pmx_jit_ode_rk4_pair<lag>"}},
       {{"pmx_jit_ode_dopri5_grid", "pmx_jit_ode_dopri5_grid<lag>"}, {"pmx_jit_ode_dopri5_pair", "pmx_jit_ode_dopri5_pair<lag>"}},
       {{"pmx_jit_ode_ros2_grid", "pmx_jit_ode_ros2_grid<lag>"}, {"pmx_jit_ode_ros2_pair", "pmx_jit_ode_ros2_pair<lag>"}},
       {{"pmx_jit_ode_rk4_checked_grid", "pmx_jit_ode_rk4_checked_grid<lag>"},
-       {"pmx_jit_ode_rk4_checked_pair", "pmx_jit_ode_rk4_checked_pair<lag>"}}};
-  static const char* const kUser[4][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
+       {"pmx_jit_ode_rk4_checked_pair", "pmx_jit_ode_rk4_checked_pair<lag>"}},
+      {{"pmx_jit_ode_auto_grid", "pmx_jit_ode_auto_grid<lag>"}, {"pmx_jit_ode_auto_pair", "pmx_jit_ode_auto_pair<lag>"}}};
+  static const char* const kUser[5][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
                                           {"pmx_jit_ode_user_dopri5_grid", "pmx_jit_ode_user_dopri5_pair"},
                                           {"pmx_jit_ode_user_ros2_grid", "pmx_jit_ode_user_ros2_pair"},
-                                          {"pmx_jit_ode_user_rk4_checked_grid", "pmx_jit_ode_user_rk4_checked_pair"}};
+                                          {"pmx_jit_ode_user_rk4_checked_grid", "pmx_jit_ode_user_rk4_checked_pair"},
+                                          {"pmx_jit_ode_user_auto_grid", "pmx_jit_ode_user_auto_pair"}};
   const int pair = r.mode == pmx::MODE_PAIR ? 1 : 0;
   switch (r.family) {
     case pmx::R_CLASSED:
@@ -397,9 +401,12 @@ Routes plan_routes(const pmx_model& model, const StreamFacts& f, const Call& c, 
   r.n = c.S;
   out.mode = r.mode;
   if (!analytical || model.custom) {
-    // (Route::solver: the PMX_SOLVER_* values are the route's solver indices)
-    static_assert(PMX_SOLVER_RK4 == 0 && PMX_SOLVER_DOPRI5 == 1 && PMX_SOLVER_ROS2 == 2 && PMX_SOLVER_RK4_CHECKED == 3, "route_name");
-    r.solver = analytical ? 0 : d.ode_solver;
+    // (Route::solver: the PMX_SOLVER_* values are the route's solver indices, except that PMX_SOLVER_AUTO = 5 - the value
+    // 4 stays refused - takes row 4)
+    static_assert(PMX_SOLVER_RK4 == 0 && PMX_SOLVER_DOPRI5 == 1 && PMX_SOLVER_ROS2 == 2 && PMX_SOLVER_RK4_CHECKED == 3 &&
+                      PMX_SOLVER_AUTO == 5,
+                  "route_name");
+    r.solver = analytical ? 0 : (d.ode_solver == PMX_SOLVER_AUTO ? 4 : d.ode_solver);
     r.lag = !analytical && !model.user_ode && model.dev.n_lag_slots > 0;
     r.family = !model.custom ? pmx::R_ODE : (analytical ? pmx::R_JIT_ANALYTICAL : (model.user_ode ? pmx::R_JIT_ODE_USER : pmx::R_JIT_ODE));
     if (model.custom && static_launcher() && r.mode == pmx::MODE_GRID && !c.ll) r.family = pmx::R_STATIC_AGRID;
@@ -462,7 +469,7 @@ int32_t jit_module(const pmx_model* model, const pmx_population* pop, const Devi
   if (it == modules.end()) {
     pmx::JitModule mod;
     const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod, pmx::jit_kind(model->jit_spec),
-                                        model->jit_spec.checked);
+                                        model->jit_spec.checked, model->jit_spec.auto_solver);
     if (le != hipSuccess) return fail(PMX_ERR_HIP, std::string("loading the compiled model: ") + hipGetErrorString(le));
     it = modules.emplace(pop->device, mod).first;
   }
@@ -476,8 +483,8 @@ int32_t launch_jit(const pmx_model* model, const pmx_population* pop, const Devi
   const pmx::JitModule* jm = nullptr;
   const int32_t rc = jit_module(model, pop, ds, &jm);
   if (rc != PMX_OK) return rc;
-  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][solver]; solver: 0 RK4, 1 adaptive, 2 checked RK4
-  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = r.solver == 3 ? 2 : (r.solver != 0 ? 1 : 0);
+  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][solver]; solver: 0 RK4, 1 adaptive, 2 checked RK4, 3 auto
+  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = r.solver == 4 ? 3 : (r.solver == 3 ? 2 : (r.solver != 0 ? 1 : 0));
   int32_t s_chunk = r.s_chunk, n_ptiles = r.n_ptiles;
   if (r.family == pmx::R_STATIC_AGRID) {
     const int rc_s = static_launcher()(&a.m, &a.ops, a.theta, a.P, a.S, s_chunk, n_ptiles, a.pred, a.ld, a.status,
@@ -499,9 +506,10 @@ int32_t launch_jit(const pmx_model* model, const pmx_population* pop, const Devi
 // device arrays, the caller's buffers
 pmx::LaunchArgs launch_args(const pmx_model* model, const pmx_population* pop, const DeviceStream* ds, const Tunables& tun,
                             const double* d_theta, int64_t P, int batch, double* d_pred, int64_t ld, uint8_t* d_status,
-                            void* stream, int state_override) {
+                            void* stream, int state_override, uint32_t* d_stats) {
   pmx::LaunchArgs a{};
   a.m = model->dev;
+  a.m.solver_stats = d_stats;  // (pmx_predict_stats_device; null otherwise)
   if (state_override >= 0) {  // Prediction::state: every output equation reads the raw amount of one state
     a.m.state_override = state_override;  // (the run-time-compiled walkers read it)
     for (int o = 0; o < PMX_MAX_OUT; ++o) {
@@ -554,7 +562,7 @@ hipError_t pmx::launch_route(const pmx::LaunchArgs& a, const pmx::Route& r) {
 }
 
 int32_t enqueue(const pmx_model* model, pmx_population* pop, const double* d_theta, int64_t P, int batch, double* d_pred,
-                int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq, int state_override) {
+                int64_t ld, uint8_t* d_status, void* stream, const LLRequest* llreq, int state_override, uint32_t* d_stats) {
   const pmx_model_desc& d = model->d;
   if (d.n_covariates != pop->hp.n_cov)
     return fail(PMX_ERR_INVALID_ARGUMENT, "model declares " + std::to_string(d.n_covariates) +
@@ -572,7 +580,7 @@ int32_t enqueue(const pmx_model* model, pmx_population* pop, const double* d_the
                 "outeq " + std::to_string(pop->hp.max_outeq) + " >= nout " + std::to_string(d.nout));
   if (pop->hp.n_subjects == 0) return PMX_OK;
 
-  pmx::LaunchArgs a = launch_args(model, pop, ds, tun, d_theta, P, batch, d_pred, ld, d_status, stream, state_override);
+  pmx::LaunchArgs a = launch_args(model, pop, ds, tun, d_theta, P, batch, d_pred, ld, d_status, stream, state_override, d_stats);
   Call call{a.S, P, batch != 0, llreq != nullptr, false, llreq ? llreq->ld : 0, state_override >= 0};
   DeviceStream::LLCache* slot = nullptr;
   struct SlotGuard {  // the slot is released (event recorded on the stream) however this function leaves

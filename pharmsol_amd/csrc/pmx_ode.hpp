@@ -68,14 +68,17 @@ __device__ __forceinline__ void rk4_step(const OdeLane<M>& L, double (&x)[M::NS]
 
 // Which stepper a walker is instantiated with (compile-time: a run-time switch between them costs the fixed-step
 // kernels their registers).
-enum : int { SOLV_RK4 = 0, SOLV_ADAPT = 1, SOLV_CHECKED = 2 };
+enum : int { SOLV_RK4 = 0, SOLV_ADAPT = 1, SOLV_CHECKED = 2, SOLV_AUTO = 3 };
 
 // ---- adaptive: Dormand-Prince 5(4) ("dopri5" / ode45), PMX_SOLVER_DOPRI5 --------------------------------------
 // One ATTEMPTED step of length h from (t, x): fills xn with the 5th-order solution and returns the scaled error
 // norm rms(e_i / (atol + rtol max(|x_i|, |xn_i|))); the step is acceptable iff the result is <= 1.
-template <class M>
+// STIFFQ (SOLV_AUTO only): also hands back the two sums of Hairer's stiffness test, aux[0] = sum (k7 - k6)^2 and
+// aux[1] = sum (xn - g6)^2, g6 = the argument of stage 6: both stages sit at t + h, so their quotient estimates |lambda|.
+template <class M, bool STIFFQ = false>
 __device__ __forceinline__ double dopri5_try(const DevModel& m, const OdeLane<M>& L, const double (&x)[M::NS],
-                                             const double (&rs)[M::NR], double t, double h, double (&xn)[M::NS]) {
+                                             const double (&rs)[M::NR], double t, double h, double (&xn)[M::NS],
+                                             double* aux = nullptr) {
   constexpr int NS = M::NS;
   double k1[NS], k2[NS], k3[NS], k4[NS], k5[NS], k6[NS], k7[NS], xt[NS];
   ode_eval<M>(t, L, x, rs, k1);
@@ -103,6 +106,17 @@ __device__ __forceinline__ double dopri5_try(const DevModel& m, const OdeLane<M>
     xn[i] = x[i] + h * ((35.0 / 384.0) * k1[i] + (500.0 / 1113.0) * k3[i] + (125.0 / 192.0) * k4[i] -
                         (2187.0 / 6784.0) * k5[i] + (11.0 / 84.0) * k6[i]);
   ode_eval<M>(t + h, L, xn, rs, k7);
+  if constexpr (STIFFQ) {
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const double dk = k7[i] - k6[i], dg = xn[i] - xt[i];
+      num += dk * dk;
+      den += dg * dg;
+    }
+    aux[0] = num;
+    aux[1] = den;
+  }
   double acc = 0.0;
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
@@ -127,15 +141,23 @@ __device__ __forceinline__ double dopri5_try(const DevModel& m, const OdeLane<M>
 // rounding for the linear compartmental bodies), the NS x NS factorisation fully unrolled in registers WITHOUT pivoting
 // (I - gamma h J of a compartmental system is a column-diagonally-dominant M-matrix, for which elimination in the natural
 // order is stable).  Same try/advance contract as DOPRI5, error exponent -1/2.
-template <class M>
+// JNORM (SOLV_AUTO only): also hands back *aux = ||J||_inf, the largest absolute row sum of the difference Jacobian
+// before its scaling by -gamma h.
+template <class M, bool JNORM = false>
 __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& L, const double (&x)[M::NS],
-                                           const double (&rs)[M::NR], double t, double h, double (&xn)[M::NS]) {
+                                           const double (&rs)[M::NR], double t, double h, double (&xn)[M::NS],
+                                           double* aux = nullptr) {
   constexpr int NS = M::NS;
   constexpr double kGamma = 1.7071067811865475;
   constexpr double kSqrtEps = 1.4901161193847656e-08;
   const double gh = kGamma * h;
   double f0[NS], f1[NS], xt[NS], W[NS][NS], ft[NS], k1[NS], k2[NS];
   ode_eval<M>(t, L, x, rs, f0);
+  [[maybe_unused]] double rowsum[NS];
+  if constexpr (JNORM) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) rowsum[i] = 0.0;
+  }
 #pragma unroll
   for (int j = 0; j < NS; ++j) {
 #pragma unroll
@@ -146,6 +168,16 @@ __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& 
     const double s = -gh / d;
 #pragma unroll
     for (int i = 0; i < NS; ++i) W[i][j] = (f1[i] - f0[i]) * s + ((i == j) ? 1.0 : 0.0);
+    if constexpr (JNORM) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) rowsum[i] += fabs(f1[i] - f0[i]) / d;
+    }
+  }
+  if constexpr (JNORM) {
+    double nj = 0.0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) nj = fmax(nj, rowsum[i]);
+    *aux = nj;
   }
   {
     const double dt = kSqrtEps * fmax(fabs(t), 1.0);
@@ -203,10 +235,22 @@ __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& 
 
 // Step-size controller state of a lane: `h` = the controller's current proposal (carried from piece to piece);
 // `failed`: step-size underflow (adaptive) / a probe found the step too coarse (checked RK4).
+// SOLV_AUTO only (no other instantiation reads or writes them): the lane's mode, the three counters of the switching
+// rule and the four statistics of pmx_predict_stats_device.
 struct AdaptState {
   double h;
   uint8_t failed;
+  uint8_t implicit;           // 0 = DOPRI5 steps, 1 = ROS2 steps
+  uint8_t stiff, calm, back;  // consecutive stiff / calm explicit steps, consecutive implicit steps DOPRI5 could take
+  uint32_t n_explicit, n_implicit, n_rejected, n_switches;
 };
+
+// a (subject, theta) pair starts explicit (where as.h is reset)
+__device__ __forceinline__ void auto_reset(AdaptState& as) {
+  as.implicit = 0;
+  as.stiff = as.calm = as.back = 0;
+  as.n_explicit = as.n_implicit = as.n_rejected = as.n_switches = 0;
+}
 
 // ---- checked RK4: the step-doubling probe, PMX_SOLVER_RK4_CHECKED -------------------------------------------------
 // The FIRST step of a piece, taken twice: xa = one step of length h (kept: a lane whose probes pass walks exactly what
@@ -273,6 +317,128 @@ __device__ __forceinline__ bool dopri5_advance(const DevModel& m, const OdeLane<
     return false;
   }
   return true;
+}
+
+// ---- auto: DOPRI5 that moves a stiff lane to ROS2 and back, PMX_SOLVER_AUTO ------------------------------------------
+// The step controller of dopri5_advance (clipping, factor clamps, no growth after a rejection, underflow); the try and
+// the error exponent follow the LANE's mode, so a wave that holds both modes runs both tries under exec masks.
+//   explicit, after an accepted step: Hairer's test of dopri5.f, h rho = h sqrt(sum (k7 - k6)^2 / sum (xn - g6)^2)
+//     (a zero denominator - a state at rest - moves no counter).  h rho > kAutoStiffRho: calm = 0, and the
+//     kAutoStiffSteps-th such step in a row switches to implicit; otherwise ++calm, and calm == kAutoCalmSteps forgets
+//     the stiff steps counted so far.
+//   implicit, after an accepted step: h ||J||_inf <= kAutoBackRho (rho <= ||J||_inf: DOPRI5 is inside its stability
+//     interval at this step, and of fifth order where ROS2 is of second) kAutoBackSteps times in a row switches back.
+// A switch keeps (t, x) and the step proposal and zeroes the three counters.
+// One thing beyond dopri5_advance's clipping: a step also ends at the next covariate knot (auto_next_knot), so a lane of
+// a model WITH interpolated covariates does not walk plain DOPRI5's steps; without covariates it does, to the bit.
+constexpr double kAutoStiffRho = 3.25;  // Hairer
+constexpr int kAutoStiffSteps = 15;     // Hairer
+constexpr int kAutoCalmSteps = 6;       // Hairer
+constexpr double kAutoBackRho = 1.0;    // (this project's: profiles/auto_solver.txt)
+constexpr int kAutoBackSteps = 6;       // (this project's)
+// The next knot of any covariate of the lane's occasion in (t, t1), or t1: segment ends of the interpolation
+// (Covariate::interpolate: a kink where two linear segments meet, a jump at a carry-forward segment).  auto_advance ends
+// its step there.  A stiff lane that has come back to DOPRI5 after its fast component died steps hours at a time, and the
+// embedded estimate of a step that straddles a kink does not see it (7.8e-5 at tolerances 1e-6 on the covariate fixture
+// of tests/test_auto_solver.py); plain DOPRI5 on such a lane never gets there, stability holds its step at 3.3 / |lambda|.
+template <class M>
+__device__ __forceinline__ double auto_next_knot(const OdeLane<M>& L, double t, double t1) {
+  double nxt = t1;
+  if constexpr (M::CUSTOM) {
+    if constexpr (M::NCOV > 0) {
+      const DevOps& ops = *L.ops;
+#pragma unroll 1
+      for (int c = 0; c < M::NCOV; ++c) {
+        const int64_t cell = L.occ * ops.n_cov + c;
+        const double tf = as_const(ops.cov_first_t)[cell];
+        if (tf > t && tf < nxt) nxt = tf;
+        const int64_t s0 = as_const(ops.cov_seg_off)[cell], s1 = as_const(ops.cov_seg_off)[cell + 1];
+#pragma unroll 1
+        for (int64_t sg = s0; sg < s1; ++sg) {
+          const double a = as_const(ops.seg_from)[sg], b = as_const(ops.seg_to)[sg];
+          if (a > t && a < nxt) nxt = a;
+          if (b > t && b < nxt) nxt = b;
+        }
+      }
+    }
+  }
+  return nxt;
+}
+
+template <class M>
+__device__ __forceinline__ bool auto_advance(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
+                                             const double (&rs)[M::NR], double& t, double t1, AdaptState& as) {
+  constexpr int NS = M::NS;
+  if (!(t1 - t > 0.0)) return false;
+  const double t_end = auto_next_knot<M>(L, t, t1);  // (t1 for a model without covariates)
+  const double left = t_end - t;
+  double h = fmin(as.h, m.rk4_h_max);
+  const bool clipped = h >= left;
+  if (clipped) h = left;
+  double xn[NS];
+  const bool stiff = as.implicit != 0;  // (per lane)
+  double aux[2] = {0.0, 0.0};
+  double err;
+  if (stiff)
+    err = ros2_try<M, true>(m, L, x, rs, t, h, xn, aux);
+  else
+    err = dopri5_try<M, true>(m, L, x, rs, t, h, xn, aux);
+  const bool ok = err <= 1.0;  // (false for NaN)
+  double fac = (err > 0.0) ? 0.9 * pow(err, stiff ? -0.5 : -0.2) : 5.0;
+  if (!(fac >= 0.2)) fac = 0.2;  // also catches NaN
+  if (fac > 5.0) fac = 5.0;
+  if (!ok && fac > 1.0) fac = 1.0;
+  const double h_next = h * fac;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) x[i] = xn[i];
+    t = clipped ? t_end : (t + h);
+    as.h = clipped ? fmax(as.h, h_next) : h_next;
+    bool sw = false;
+    if (stiff) {
+      ++as.n_implicit;
+      if (h * aux[0] <= kAutoBackRho) {
+        if (++as.back == kAutoBackSteps) sw = true;
+      } else {
+        as.back = 0;
+      }
+    } else {
+      ++as.n_explicit;
+      if (aux[1] > 0.0) {
+        if (h * sqrt(aux[0] / aux[1]) > kAutoStiffRho) {
+          as.calm = 0;
+          if (++as.stiff == kAutoStiffSteps) sw = true;
+        } else if (++as.calm == kAutoCalmSteps) {
+          as.stiff = 0;
+        }
+      }
+    }
+    if (sw) {
+      as.implicit = stiff ? 0 : 1;
+      as.stiff = as.calm = as.back = 0;
+      ++as.n_switches;
+    }
+    return !(clipped && t_end >= t1);
+  }
+  ++as.n_rejected;
+  as.h = h_next;
+  if (!(h_next > 1.0e-13 * fmax(1.0, fabs(t)))) {  // step-size underflow (or NaN): give up on this piece
+    as.failed = 1;
+    t = t1;
+    return false;
+  }
+  return true;
+}
+
+// a pair's statistics record, stored where the pair stores its status byte (DevModel::solver_stats, null otherwise)
+__device__ __forceinline__ void auto_store_stats(const DevModel& m, const AdaptState& as, int64_t pair) {
+  if (m.solver_stats != nullptr) {
+    uint32_t* __restrict__ r = m.solver_stats + pair * 4;
+    r[0] = as.n_explicit;
+    r[1] = as.n_implicit;
+    r[2] = as.n_rejected;
+    r[3] = as.n_switches;
+  }
 }
 
 template <class M>
@@ -401,6 +567,12 @@ __device__ __forceinline__ void ode_piece(const DevModel& m, const OdeLane<M>& L
     }
     return;
   }
+  if constexpr (SOLV == SOLV_AUTO) {
+    double t = t0;
+    for (int32_t guard = 0; guard < 10000000 && auto_advance<M>(m, L, x, rs, t, t1, as); ++guard) {
+    }
+    return;
+  }
   double nf = ceil(dt / m.rk4_h_max);
   if (!(nf >= 1.0)) nf = 1.0;
   if (nf > 1.0e7) nf = 1.0e7;  // a lane with an absurd lag must still terminate
@@ -501,7 +673,7 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
                                               int64_t P, int64_t S, int32_t s_chunk, int32_t n_ptiles,
                                               double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {
   constexpr int NS = M::NS;
-  constexpr bool ADAPT = SOLV == SOLV_ADAPT, CHECKED = SOLV == SOLV_CHECKED;
+  constexpr bool AUTO = SOLV == SOLV_AUTO, ADAPT = SOLV == SOLV_ADAPT || AUTO, CHECKED = SOLV == SOLV_CHECKED;
   const int64_t b = blockIdx.x;
   const int32_t ptile = static_cast<int32_t>(b % n_ptiles);
   const int64_t chunk = b / n_ptiles;
@@ -541,6 +713,7 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
     AdaptState as;  // adaptive solver: the step-size proposal restarts with every subject
     as.h = m.rk4_h_max;
     as.failed = 0;
+    if constexpr (AUTO) auto_reset(as);
     double clk = 0.0;  // LAG: the lane's solver clock (see ode_lag_open_occasion)
     for (int64_t o = o0; o < o1; ++o) {
       const uint32_t meta = uniform32(as_const(ops.op_meta)[o]);
@@ -555,7 +728,7 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
           ode_lag_prop<M, SOLV>(m, ops, ls, (clk > t0) ? clk : t0, t1, L, rs, th, x, as);
           if (t1 > clk) clk = t1;
         } else if constexpr (ADAPT) {
-          ode_piece<M, SOLV_ADAPT>(m, L, x, rs, uniformf64(as_const(ops.op_t0)[o]), uniformf64(as_const(ops.op_t1)[o]), as);
+          ode_piece<M, SOLV>(m, L, x, rs, uniformf64(as_const(ops.op_t0)[o]), uniformf64(as_const(ops.op_t1)[o]), as);
         } else {
           const double h = uniformf64(as_const(ops.op_b)[o]);
           const int32_t n = static_cast<int32_t>(uniform32(static_cast<uint32_t>(as_const(ops.op_n)[o])));
@@ -603,6 +776,9 @@ __device__ __forceinline__ void ode_grid_body(const DevModel& m, const DevOps& o
       if (lane_ok) ops.ll_out[s * ops.ll_ld + p] = (st == PMX_PAIR_OK || st == PMX_PAIR_NONFINITE) ? ll_acc : nanv;
     }
     if (status != nullptr && lane_ok) status[s * P + p] = st;  // every pair writes its byte: no memset before the launch
+    if constexpr (AUTO) {
+      if (lane_ok) auto_store_stats(m, as, s * P + p);
+    }
   }
 }
 
@@ -615,7 +791,7 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
                                               int64_t P, int64_t S, int32_t batch, double* __restrict__ pred,
                                               int64_t ld, uint8_t* __restrict__ status) {
   constexpr int NS = M::NS;
-  constexpr bool ADAPT = SOLV == SOLV_ADAPT, CHECKED = SOLV == SOLV_CHECKED;
+  constexpr bool AUTO = SOLV == SOLV_AUTO, ADAPT = SOLV == SOLV_ADAPT || AUTO, CHECKED = SOLV == SOLV_CHECKED;
   const int64_t n_pairs = batch ? S : S * P;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const bool lane_ok = i < n_pairs;
@@ -672,6 +848,7 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
   AdaptState as;
   as.h = m.rk4_h_max;
   as.failed = 0;
+  if constexpr (AUTO) auto_reset(as);
   double ll_acc = 0.0;
   // LAG: an open PROP (or occasion opening) [t_cur, t_stop) that lagged boluses may still split
   bool in_prop = false;
@@ -856,7 +1033,9 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
       // op waits for at most that many steps of its neighbours, not for the longest piece in the wave; the host
       // picks the bound from the batch size (pmx_launch.cpp).
       const int32_t spt = ops.steps_per_trip;
-      if constexpr (ADAPT) {
+      if constexpr (AUTO) {
+        for (int32_t j = 0; j < spt && stepping; ++j) stepping = auto_advance<M>(m, L, x, rs, t_run, t_run_end, as);
+      } else if constexpr (ADAPT) {
         for (int32_t j = 0; j < spt && stepping; ++j) stepping = dopri5_advance<M>(m, L, x, rs, t_run, t_run_end, as);
       } else {
         const int32_t kk = rem < spt ? rem : spt;
@@ -885,6 +1064,9 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
     if (lane_ok) ops.ll_out[batch ? s : (s * ops.ll_ld + p)] = (st == PMX_PAIR_OK || st == PMX_PAIR_NONFINITE) ? ll_acc : nanv;
   }
   if (status != nullptr && lane_ok) status[batch ? s : (s * P + p)] = st;  // every pair writes its byte
+  if constexpr (AUTO) {
+    if (lane_ok) auto_store_stats(m, as, batch ? s : (s * P + p));
+  }
 }
 
 }  // namespace

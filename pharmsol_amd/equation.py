@@ -554,14 +554,21 @@ class ODE(Equation):
         fixed-step walk of ``"rk4"`` with a step-doubling probe at the head of every integration piece: a support point
         whose rates ``h_max`` does not resolve (Richardson estimate of the first step's error beyond ``with_tolerances``)
         comes back NaN from that piece on, with pair status ``PMX_PAIR_STEP_TOO_COARSE``, instead of finite nonsense;
-        every other pair gets plain RK4's numbers."""
-        self.ode_solver = {"rk4": _abi.PMX_SOLVER_RK4, "dopri5": _abi.PMX_SOLVER_DOPRI5, "ros2": _abi.PMX_SOLVER_ROS2,
-                           "stiff": _abi.PMX_SOLVER_ROS2, "rk4-checked": _abi.PMX_SOLVER_RK4_CHECKED}[solver]
+        every other pair gets plain RK4's numbers.  ``"auto"`` (alias ``"lsoda"``) = ``"dopri5"`` that detects stiffness
+        per lane (Hairer's test after every accepted step), moves a stiff lane to ``"ros2"`` steps and back when the
+        step has come inside the explicit method's stability interval; a lane that never switches walks what
+        ``"dopri5"`` walks (``runtime.predict(..., solver_stats=True)`` counts the steps of each kind per pair)."""
+        names = {"rk4": _abi.PMX_SOLVER_RK4, "dopri5": _abi.PMX_SOLVER_DOPRI5, "ros2": _abi.PMX_SOLVER_ROS2,
+                 "stiff": _abi.PMX_SOLVER_ROS2, "rk4-checked": _abi.PMX_SOLVER_RK4_CHECKED, "auto": _abi.PMX_SOLVER_AUTO,
+                 "lsoda": _abi.PMX_SOLVER_AUTO}
+        if solver not in names:
+            raise KeyError(f"unknown solver {solver!r}: one of " + ", ".join(repr(k) for k in names))
+        self.ode_solver = names[solver]
         self._handle = None
         return self
 
     def with_tolerances(self, rtol: float, atol: float) -> "ODE":
-        """``ODE::with_tolerances`` (ode/mod.rs:152-166); read by the adaptive solvers and by ``"rk4-checked"``'s probe."""
+        """``ODE::with_tolerances`` (ode/mod.rs:152-166); read by the adaptive solvers (``"auto"`` included) and by ``"rk4-checked"``'s probe."""
         self.ode_rtol, self.ode_atol = float(rtol), float(atol)
         self._handle = None
         return self

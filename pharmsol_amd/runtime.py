@@ -268,9 +268,12 @@ def predict_host(model, flat: FlatPopulation, theta: np.ndarray, device: int = 0
     return pred, status
 
 
-def predict(model, pop: DevicePopulation, theta, pred=None, status=None, batch: bool = False, want_status: bool = True):
+def predict(model, pop: DevicePopulation, theta, pred=None, status=None, batch: bool = False, want_status: bool = True,
+            solver_stats: bool = False):
     """Device-pointer ABI form (``pmx_predict_device``): torch CUDA tensors, enqueued on torch's
-    current stream, not synchronised.  Returns ``(pred, status)`` tensors."""
+    current stream, not synchronised.  Returns ``(pred, status)`` tensors.  ``solver_stats=True`` (models of
+    ``with_solver("auto")`` only, ``pmx_predict_stats_device``): a third value, the int32 tensor ``[n_subjects, n_support, 4]``
+    (batch: ``[n_subjects, 4]``) of accepted explicit steps, accepted implicit steps, rejected attempts and switches."""
     import torch
 
     L = _ffi.lib()
@@ -281,14 +284,24 @@ def predict(model, pop: DevicePopulation, theta, pred=None, status=None, batch: 
     theta = theta.contiguous()
     assert theta.dtype == torch.float64 and theta.dim() == 2 and theta.shape[1] == dm.desc.nparams
     stream = torch.cuda.current_stream(dev).cuda_stream
+    stats = None
+    if solver_stats:
+        if dm.desc.ode_solver != _abi.PMX_SOLVER_AUTO:
+            raise ValueError("solver_stats=True needs a model of with_solver('auto')")
+        n_pairs = (pop.n_subjects,) if batch else (pop.n_subjects, int(theta.shape[0]))
+        stats = torch.zeros(n_pairs + (4,), dtype=torch.int32, device=dev)
     if batch:
         assert theta.shape[0] == pop.n_subjects
         if pred is None:
             pred = torch.empty((pop.n_observations,), dtype=torch.float64, device=dev)
         if status is None and want_status:
             status = torch.zeros((pop.n_subjects,), dtype=torch.uint8, device=dev)
-        rc = L.pmx_predict_batch_device(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(),
-                                        status.data_ptr() if status is not None else None, stream)
+        if solver_stats:
+            rc = L.pmx_predict_batch_stats_device(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(),
+                                                  status.data_ptr() if status is not None else None, stream, stats.data_ptr())
+        else:
+            rc = L.pmx_predict_batch_device(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(),
+                                            status.data_ptr() if status is not None else None, stream)
     else:
         P = int(theta.shape[0])
         if pred is None:
@@ -297,9 +310,15 @@ def predict(model, pop: DevicePopulation, theta, pred=None, status=None, batch: 
         ld = int(pred.stride(0)) if pred.dim() == 2 and pred.shape[0] > 1 else P
         if status is None and want_status:
             status = torch.zeros((pop.n_subjects, P), dtype=torch.uint8, device=dev)
-        rc = L.pmx_predict_device(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), ld,
-                                  status.data_ptr() if status is not None else None, stream)
+        if solver_stats:
+            rc = L.pmx_predict_stats_device(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), ld,
+                                            status.data_ptr() if status is not None else None, stream, stats.data_ptr())
+        else:
+            rc = L.pmx_predict_device(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), ld,
+                                      status.data_ptr() if status is not None else None, stream)
     _ffi.check(rc)
+    if solver_stats:
+        return pred, status, stats
     return pred, status
 
 

@@ -1,0 +1,468 @@
+"""PMX_SOLVER_AUTO (``ODE.with_solver("auto")``, alias ``"lsoda"``): DOPRI5 that detects stiffness per lane, moves that
+lane to ROS2 and back (csrc/pmx_ode.hpp auto_advance).  The rule, restated here in numpy:
+
+  one step controller for both methods (dopri5_advance's: clipping to the piece end and to h_max, factor
+  0.9 err^(-1/5 | -1/2) in [0.2, 5], no growth after a rejection, underflow); try and exponent follow the lane's mode.
+  explicit, after an accepted step (Hairer, dopri5.f): h rho = h sqrt(sum (k7 - k6)^2 / sum (xn - g6)^2); a zero
+    denominator moves no counter; h rho > 3.25: calm = 0, the 15th such step in a row switches to implicit; otherwise
+    ++calm and calm == 6 sets stiff = 0.
+  implicit, after an accepted step: h ||J||_inf <= 1.0 (largest absolute row sum of ros2_try's difference Jacobian):
+    the 6th such step in a row switches to explicit; otherwise back = 0.
+  a switch keeps (t, x) and the step proposal and zeroes the three counters.
+  a model with interpolated covariates: a step also ends at the next covariate knot (auto_next_knot; none in the
+    restatement's autonomous bodies).
+
+Plain f64 without FMA here; the device contracts, so the GPU tests compare through the library (auto against dopri5 /
+ros2 on the same device) and against closed forms, never step for step against this file.  The oracle has no auto mode."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle
+from pharmsol_amd import ODE, Analytical, Data, Ratio, Subject, _abi, _ffi, runtime
+from tests.test_custom_models import rel_err_floor
+from tests.test_stiff_solver import _oral_subjects, _stiff_theta
+
+# ------------------------------------------------------------------------------------- the rule in numpy
+STIFF_RHO, STIFF_STEPS, CALM_STEPS = 3.25, 15, 6  # Hairer's
+BACK_RHO, BACK_STEPS = 1.0, 6                     # this project's
+GAMMA = 1.7071067811865475
+SQRT_EPS = 1.4901161193847656e-08
+
+
+def dopri5_try(f, x, h, tol):
+    k1 = f(x)
+    k2 = f(x + h * (0.2 * k1))
+    k3 = f(x + h * ((3.0 / 40.0) * k1 + (9.0 / 40.0) * k2))
+    k4 = f(x + h * ((44.0 / 45.0) * k1 - (56.0 / 15.0) * k2 + (32.0 / 9.0) * k3))
+    k5 = f(x + h * ((19372.0 / 6561.0) * k1 - (25360.0 / 2187.0) * k2 + (64448.0 / 6561.0) * k3 - (212.0 / 729.0) * k4))
+    g6 = x + h * ((9017.0 / 3168.0) * k1 - (355.0 / 33.0) * k2 + (46732.0 / 5247.0) * k3 + (49.0 / 176.0) * k4
+                  - (5103.0 / 18656.0) * k5)
+    k6 = f(g6)
+    xn = x + h * ((35.0 / 384.0) * k1 + (500.0 / 1113.0) * k3 + (125.0 / 192.0) * k4 - (2187.0 / 6784.0) * k5
+                  + (11.0 / 84.0) * k6)
+    k7 = f(xn)
+    e = h * ((71.0 / 57600.0) * k1 - (71.0 / 16695.0) * k3 + (71.0 / 1920.0) * k4 - (17253.0 / 339200.0) * k5
+             + (22.0 / 525.0) * k6 - (1.0 / 40.0) * k7)
+    sc = tol + tol * np.maximum(np.abs(x), np.abs(xn))
+    return xn, float(np.sqrt(np.mean((e / sc) ** 2))), float(np.sum((k7 - k6) ** 2)), float(np.sum((xn - g6) ** 2))
+
+
+def ros2_try(f, x, h, tol):
+    """(autonomous right-hand sides: the f_t term is exactly zero)"""
+    n = len(x)
+    gh = GAMMA * h
+    f0 = f(x)
+    W, rows = np.empty((n, n)), np.zeros(n)
+    for j in range(n):
+        xt = x.copy()
+        d = SQRT_EPS * max(abs(x[j]), 1.0)
+        xt[j] = x[j] + d
+        df = f(xt) - f0
+        W[:, j] = df * (-gh / d)
+        W[j, j] += 1.0
+        rows += np.abs(df) / d
+    k1 = np.linalg.solve(W, f0)
+    k2 = np.linalg.solve(W, f(x + h * k1) - 2.0 * k1)
+    xn = x + h * (1.5 * k1 + 0.5 * k2)
+    e = (0.5 * h) * (k1 + k2)
+    sc = tol + tol * np.maximum(np.abs(x), np.abs(xn))
+    return xn, float(np.sqrt(np.mean((e / sc) ** 2))), float(rows.max())
+
+
+def walk(f, x0, pieces, tol, h_max, solver):
+    """solver: "dopri5" | "ros2" | "auto".  -> (states at the piece ends, [explicit, implicit, rejected, switches])"""
+    x, hprop = np.array(x0, dtype=float), h_max
+    implicit = solver == "ros2"
+    stiff = calm = back = 0
+    n_e = n_i = n_r = n_s = 0
+    out = []
+    for (t, t1) in pieces:
+        while True:
+            left = t1 - t
+            if not left > 0.0:
+                break
+            h = min(hprop, h_max)
+            clipped = h >= left
+            if clipped:
+                h = left
+            if implicit:
+                xn, err, nj = ros2_try(f, x, h, tol)
+            else:
+                xn, err, num, den = dopri5_try(f, x, h, tol)
+            ok = err <= 1.0
+            fac = 0.9 * err ** (-0.5 if implicit else -0.2) if err > 0.0 else 5.0
+            if not fac >= 0.2:
+                fac = 0.2
+            if fac > 5.0:
+                fac = 5.0
+            if not ok and fac > 1.0:
+                fac = 1.0
+            h_next = h * fac
+            if not ok:
+                n_r += 1
+                hprop = h_next
+                assert h_next > 1e-13 * max(1.0, abs(t))
+                continue
+            x, t = xn, (t1 if clipped else t + h)
+            hprop = max(hprop, h_next) if clipped else h_next
+            sw = False
+            if implicit:
+                n_i += 1
+                if solver == "auto":
+                    if h * nj <= BACK_RHO:
+                        back += 1
+                        sw = back == BACK_STEPS
+                    else:
+                        back = 0
+            else:
+                n_e += 1
+                if solver == "auto" and den > 0.0:
+                    if h * np.sqrt(num / den) > STIFF_RHO:
+                        calm, stiff = 0, stiff + 1
+                        sw = stiff == STIFF_STEPS
+                    else:
+                        calm += 1
+                        if calm == CALM_STEPS:
+                            stiff = 0
+            if sw:
+                implicit, stiff, calm, back, n_s = not implicit, 0, 0, 0, n_s + 1
+            if clipped:
+                break
+        out.append(x.copy())
+    return np.array(out), [n_e, n_i, n_r, n_s]
+
+
+def _two_cmt_oral(ke, ka, kcp, kpc):
+    return np.array([[-ka, 0.0, 0.0], [ka, -(ke + kcp), kpc], [0.0, kcp, -kpc]])
+
+
+def _one_cmt_oral(ka, ke):
+    return np.array([[-ka, 0.0], [ka, -ke]])
+
+
+def _exact(A, x0, times):
+    from scipy.linalg import expm
+
+    return np.array([expm(A * t) @ np.asarray(x0, dtype=float) for t in times])
+
+
+PIECES = [(0.0, 24.0), (24.0, 48.0)]
+
+
+def _three_walks(A, x0, tol, central, explicit_too=True):
+    """-> {solver: (relative error on the central state against expm, counts, states)}"""
+    want = _exact(A, x0, [24.0, 48.0])[:, central]
+    res = {}
+    for s in ("auto", "ros2") + (("dopri5",) if explicit_too else ()):
+        xs, counts = walk(lambda x: A @ x, x0, PIECES, tol, 48.0, s)
+        res[s] = (float((np.abs(xs[:, central] - want) / np.abs(want)).max()), counts, xs)
+    return res
+
+
+# (ka, tol, DOPRI5 run too?): the rows of profiles/auto_solver.txt; at ka = 5e5 DOPRI5 is stability-bound at
+# 48 ka / 3.3 = 7.3e6 steps and is not run - that figure stands in for its count
+ROWS = [(1.0, 1e-6, True), (20.0, 1e-6, True), (200.0, 1e-6, True), (1000.0, 1e-6, True), (5000.0, 1e-6, True),
+        (5.0e5, 1e-5, False)]
+
+
+@pytest.mark.parametrize("ka,tol,explicit_too", ROWS)
+def test_rule_restated_three_states(ka, tol, explicit_too):
+    res = _three_walks(_two_cmt_oral(0.1, ka, 0.5, 0.3), [100.0, 0.0, 0.0], tol, 1, explicit_too)
+    singles = ["ros2"] + (["dopri5"] if explicit_too else [])
+    err, counts, xs = res["auto"]
+    attempts = sum(counts[:3])
+    print(ka, tol, {k: (f"{v[0]:.2e}", v[1]) for k, v in res.items()})
+    assert err <= 2.0 * max(res[s][0] for s in singles)
+    single_counts = [sum(res[s][1][:3]) for s in singles] + ([] if explicit_too else [48.0 * ka / 3.3])
+    assert attempts <= 1.5 * min(single_counts)
+    if ka == 1.0:  # a lane that never switches walks exactly what DOPRI5 walks
+        assert counts[1] == 0 and counts[3] == 0
+        assert counts == res["dopri5"][1] and np.array_equal(xs, res["dopri5"][2])
+    if ka >= 200.0:
+        assert counts[1] > 0 and counts[3] >= 1
+
+
+def test_rule_restated_two_states():
+    x0 = [100.0, 0.0]
+    calm = _three_walks(_one_cmt_oral(1.0, 0.1), x0, 1e-6, 1)
+    assert calm["auto"][1][1] == 0 and calm["auto"][1][3] == 0
+    assert calm["auto"][1] == calm["dopri5"][1] and np.array_equal(calm["auto"][2], calm["dopri5"][2])
+    stiff = _three_walks(_one_cmt_oral(1000.0, 0.1), x0, 1e-6, 1)
+    err, counts, _ = stiff["auto"]
+    assert counts[1] > 0 and counts[3] >= 1
+    assert err <= 2.0 * max(stiff["ros2"][0], stiff["dopri5"][0])
+    assert sum(counts[:3]) <= 1.5 * min(sum(stiff["ros2"][1][:3]), sum(stiff["dopri5"][1][:3]))
+
+
+# ------------------------------------------------------------------------------------- host path (no GPU)
+def _builtin(solver="auto", tol=1e-6):
+    return (ODE.new("two_cmt_oral", {0: Ratio(1, 4)}, nparams=5, h_max=48.0).with_nstates(3).with_ndrugs(1).with_nout(1)
+            .with_solver(solver).with_tolerances(tol, tol))
+
+
+def _closed_form():
+    return (Analytical.new("two_compartments_with_absorption", {0: Ratio(1, 4)}, nparams=5).with_nstates(3).with_ndrugs(1)
+            .with_nout(1))
+
+
+def test_enum_and_descriptor():
+    assert _abi.PMX_SOLVER_AUTO == 5
+    assert _builtin("auto").desc().ode_solver == 5 and _builtin("lsoda").desc().ode_solver == 5
+    assert _builtin("rk4").desc().ode_solver == 0  # the default stays
+    assert ODE.new("one_cmt_iv", {0: Ratio(0, 1)}, nparams=2).desc().ode_solver == _abi.PMX_SOLVER_RK4
+    with pytest.raises(KeyError) as e:
+        _builtin("lsode")
+    assert "'auto'" in str(e.value) and "'lsoda'" in str(e.value)
+
+
+def test_model_create_accepts_the_solver_and_wants_tolerances():
+    L = _ffi.lib()
+    d = _builtin().desc()
+    h = C.c_void_p()
+    assert L.pmx_model_create(C.byref(d), C.byref(h)) == _abi.PMX_OK
+    L.pmx_model_destroy(h)
+    for field in ("ode_rtol", "ode_atol"):
+        bad = _builtin().desc()
+        setattr(bad, field, 0.0)
+        assert L.pmx_model_create(C.byref(bad), C.byref(h)) == _abi.PMX_ERR_INVALID_ARGUMENT
+
+
+def test_stats_entry_points_refuse_other_solvers_before_touching_a_device():
+    L = _ffi.lib()
+    for solver in ("rk4", "dopri5", "ros2"):
+        d = _builtin(solver).desc()
+        h = C.c_void_p()
+        assert L.pmx_model_create(C.byref(d), C.byref(h)) == _abi.PMX_OK
+        assert L.pmx_predict_stats_device(h, None, None, 1, None, 1, None, None, None) == _abi.PMX_ERR_INVALID_ARGUMENT
+        assert "PMX_SOLVER_AUTO" in L.pmx_last_error().decode()
+        assert L.pmx_predict_batch_stats_device(h, None, None, None, None, None, None) == _abi.PMX_ERR_INVALID_ARGUMENT
+        assert "PMX_SOLVER_AUTO" in L.pmx_last_error().decode()
+        L.pmx_model_destroy(h)
+
+
+SIG = ("double t, const double* x, const double* p, const double* cov, const double* rateiv, "
+       "const double* derived, double* ")
+ORAL_SRC = f"""
+PMX_DEVICE void pmx_dynamics({SIG}dx) {{
+  dx[0] = -p[0] * x[0];
+  dx[1] = p[0] * x[0] - p[1] * x[1] + rateiv[0];
+}}
+PMX_DEVICE void pmx_outputs({SIG}y) {{ y[0] = x[1]; }}
+"""
+ORAL_LAG_SRC = ORAL_SRC + f"PMX_DEVICE void pmx_route_lag({SIG}lag) {{ lag[0] = p[2]; }}\n"
+
+
+def _custom(solver="auto", tol=1e-6):
+    return ODE.custom(ORAL_SRC, nstates=2, nparams=2, h_max=24.0).with_solver(solver).with_tolerances(tol, tol)
+
+
+def _user_lag(solver="auto", tol=1e-6):
+    return (ODE.user(ORAL_LAG_SRC, nstates=2, nparams=3, ndrugs=1, nout=1, h_max=24.0).with_solver(solver)
+            .with_tolerances(tol, tol))
+
+
+def test_hiprtc_models_compile_the_auto_entry_points_only_when_asked():
+    tu = runtime.jit_translation_unit(_custom())
+    assert tu.count('extern "C" __global__') == 8 and tu.count("pmx::SOLV_AUTO>") == 8  # grid/pair x lag x loglik
+    plain = runtime.jit_translation_unit(_custom("rk4"))
+    assert plain.count('extern "C" __global__') == 16 and "SOLV_AUTO>" not in plain
+    runtime.DeviceModel(_custom())  # hiprtc compiles for gfx950 without a device
+    runtime.DeviceModel(_user_lag())
+    bad = _custom().with_tolerances(0.0, 1e-4)
+    with pytest.raises(_abi.PmxError) as e:
+        runtime.DeviceModel(bad)
+    assert e.value.status == _abi.PMX_ERR_INVALID_ARGUMENT
+
+
+# ------------------------------------------------------------------------------------- device
+def _gpu(model, flat, theta, batch=False, stats=False):
+    import torch
+
+    pop = runtime.DevicePopulation(flat, 0)
+    out = runtime.predict(model, pop, np.ascontiguousarray(theta), batch=batch, solver_stats=stats)
+    torch.cuda.synchronize()
+    return tuple(o.cpu().numpy() for o in out) + (runtime.last_kernel_name(),)
+
+
+def _calm_theta(rng, n):
+    """[ke, ka, kcp, kpc, v] of a lane that is NOT stiff at the tolerances used here.  Stiff is relative to the step the
+    accuracy allows: at 1e-6 DOPRI5's smooth-tail step on these subjects is 1 to 2 h, so Hairer's h rho > 3.25 starts at
+    rho of about 2 to 3 /h.  ka 0.5 to 3 /h; the distribution rates are of the size of the row the rule's constants were
+    tried on (kcp 0.5, kpc 0.3): kcp 0.2 to 0.6, kpc 0.1 to 0.4.  On this class the numpy restatement above, run over the
+    40 subjects x 35 columns of the mixed-wave test at 1e-6, never counts one stiff step (largest counter 0 of 15).  With
+    the distribution rates of _stiff_theta (kcp up to 2, kpc up to 1) it sits in the band where the rule flaps: 1 pair of
+    140 takes 6 implicit steps."""
+    return np.stack([rng.uniform(0.05, 0.3, n), rng.uniform(0.5, 3.0, n), rng.uniform(0.2, 0.6, n), rng.uniform(0.1, 0.4, n),
+                     rng.uniform(10, 50, n)], axis=1)
+
+
+LANE_MAPPINGS = [(70, False), (4, False), (0, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_support,batch", LANE_MAPPINGS)
+def test_gpu_lanes_that_never_switch_walk_what_dopri5_walks(n_support, batch):
+    rng = np.random.default_rng(81)
+    subs = _oral_subjects(rng, 40)
+    ma, md = _builtin("auto", 1e-8), _builtin("dopri5", 1e-8)
+    flat = ma.flatten(Data(subs))
+    th = _calm_theta(rng, len(subs) if batch else n_support)
+    got, st, stats, name = _gpu(ma, flat, th, batch, stats=True)
+    assert name == ("pmx_ode_auto_pair" if (batch or n_support < 32) else "pmx_ode_auto_grid")
+    want, wst, _ = _gpu(md, flat, th, batch)
+    np.testing.assert_array_equal(st, wst)
+    assert (st == 0).all()
+    err = (np.abs(got - want) / np.abs(want)).max()
+    print("auto vs dopri5, max relative difference:", err)
+    assert err <= 1e-6
+    stats = stats.reshape(-1, 4)
+    assert stats.shape[0] == st.size
+    assert (stats[:, 3] == 0).all() and (stats[:, 1] == 0).all() and (stats[:, 0] > 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_support,batch", LANE_MAPPINGS)
+def test_gpu_mixed_wave_of_stiff_and_calm_lanes(n_support, batch):
+    rng = np.random.default_rng(82)
+    subs = _oral_subjects(rng, 40)
+    n = len(subs) if batch else n_support
+    th = _calm_theta(rng, n)
+    hot = _stiff_theta(rng, n)
+    hot[:, 1] = np.exp(rng.uniform(np.log(1000.0), np.log(5000.0), n))
+    th[1::2] = hot[1::2]  # odd columns (batch: odd subjects) are stiff
+    mc = _closed_form()
+    exact, _ = (oracle.predict_batch if batch else oracle.predict)(mc, mc.flatten(Data(subs)), th)
+    flat = _builtin().flatten(Data(subs))
+    if batch:  # prediction rows of odd subjects
+        off = runtime.DevicePopulation(flat, 0).observation_offsets()
+        odd = np.zeros(exact.shape[0], dtype=bool)
+        for s in range(1, len(subs), 2):
+            odd[off[s]:off[s + 1]] = True
+        classes = {"calm": (~odd,), "stiff": (odd,)}
+    else:
+        classes = {"calm": (slice(None), slice(0, None, 2)), "stiff": (slice(None), slice(1, None, 2))}
+    err, stats = {}, None
+    for solver in ("auto", "dopri5", "ros2"):
+        out = _gpu(_builtin(solver), flat, th, batch, stats=solver == "auto")
+        got, st = out[0], out[1]
+        assert (st == 0).all(), solver
+        if solver == "auto":
+            stats = out[2]
+            assert out[-1] == ("pmx_ode_auto_pair" if (batch or n_support < 32) else "pmx_ode_auto_grid")
+        e = rel_err_floor(got, exact)
+        err[solver] = {k: float(e[ix].max()) for k, ix in classes.items()}
+    print(err)
+    for k in classes:
+        assert err["auto"][k] <= 2.0 * max(err["dopri5"][k], err["ros2"][k]), (k, err)
+    stiff_stats = stats[1::2] if batch else stats[:, 1::2]
+    calm_stats = stats[0::2] if batch else stats[:, 0::2]
+    assert (stiff_stats[..., 1] > 0).all() and (stiff_stats[..., 3] >= 1).all()
+    assert (calm_stats[..., 1] == 0).all()
+
+
+@pytest.mark.gpu
+def test_gpu_the_case_no_explicit_method_can_do():
+    """ka = 5e5 /h: DOPRI5 is stability-bound at 48 ka / 3.3 = 7.3e6 steps; auto resolves the transient explicitly,
+    switches, and stays under 1 % of that count (the numpy restatement takes 1 534 attempts)."""
+    s = Subject.builder("s").bolus(0.0, 100.0, 0).missing_observation(24.0, 0).missing_observation(48.0, 0).build()
+    th = np.array([[0.1, 5.0e5, 0.5, 0.3, 20.0]])
+    mc = _closed_form()
+    exact, _ = oracle.predict(mc, mc.flatten(s), th)
+    ma, mr = _builtin("auto", 1e-5), _builtin("ros2", 1e-5)
+    flat = ma.flatten(s)
+    got, st, stats, _ = _gpu(ma, flat, th, stats=True)
+    ros, rst, _ = _gpu(mr, flat, th)
+    assert (st == 0).all() and (rst == 0).all()
+    e_auto, e_ros = rel_err_floor(got, exact).max(), rel_err_floor(ros, exact).max()
+    print("auto", e_auto, "ros2", e_ros, "stats", stats.reshape(-1))
+    assert e_auto <= 2.0 * e_ros
+    n_e, n_i, n_r, n_s = (int(v) for v in stats.reshape(-1))
+    assert n_e + n_i + n_r <= 72727
+    assert n_s >= 1
+
+
+@pytest.mark.gpu
+def test_gpu_custom_body_with_lag_covariate_and_likelihood():
+    """The body of test_gpu_ros2_custom_body_with_lag_covariate_and_likelihood (tests/test_stiff_solver.py) under auto:
+    a time-varying covariate in the right-hand side (ROS2's f_t term), a lag time, the fused likelihood.
+
+    The covariate is linear on [0, 24] and constant after: a knot at t = 24.  A stiff lane (ka 50 to 2000) goes implicit
+    after the transient, comes back to DOPRI5 when piece ends have cut ROS2's steps short (infusion at 5 h), and - the fast
+    component being numerically zero by then - steps 2 to 3 h at a time.  A step that straddles the knot is judged by an
+    embedded estimate that does not see the kink: 7.8e-5 here against ROS2's 1.0e-5 before auto_advance ended its steps
+    at covariate knots (auto_next_knot), 9.2e-6 with it."""
+    from pharmsol_amd import AssayErrorModel, AssayErrorModels, ErrorPoly
+
+    rng = np.random.default_rng(74)
+    src = """
+    PMX_DEVICE void pmx_dynamics(double t, const double* x, const double* p, const double* cov, const double* rateiv,
+                                 const double* derived, double* dx) {
+      const double ke = p[1] * (cov[0] / 70.0);
+      dx[0] = -p[0] * x[0];
+      dx[1] = p[0] * x[0] - ke * x[1] + rateiv[0];
+    }
+    PMX_DEVICE void pmx_outputs(double t, const double* x, const double* p, const double* cov, const double* rateiv,
+                                const double* derived, double* y) { y[0] = x[1] / p[2]; }
+    """
+
+    def model(solver, tol):
+        m = (ODE.custom(src, nstates=2, nparams=4, covariates=["wt"], lag={0: 3}, h_max=24.0).with_solver(solver)
+             .with_tolerances(tol, tol))
+        m.bolus_dest = {0: 0}
+        return m
+
+    subs = []
+    for i in range(20):
+        b = Subject.builder(f"c{i}").bolus(0.0, float(rng.uniform(100, 500)), 0).infusion(5.0, 200.0, 0, 1.5)
+        for t in sorted(rng.uniform(0.1, 36, 6)):
+            b = b.observation(float(t), float(rng.uniform(0.5, 5.0)), 0)
+        subs.append(b.covariate("wt", 0.0, float(rng.uniform(50, 100))).covariate("wt", 24.0, float(rng.uniform(50, 100))).build())
+    th = np.stack([np.exp(rng.uniform(np.log(50.0), np.log(2000.0), 64)), rng.uniform(0.05, 0.4, 64), rng.uniform(10, 50, 64),
+                   rng.uniform(0.0, 2.0, 64)], axis=1)
+    fine = model("dopri5", 1e-8)
+    flat = fine.flatten(Data(subs))
+    want, wst, _ = _gpu(fine, flat, th)
+    ros, rst, _ = _gpu(model("ros2", 1e-6), flat, th)
+    got, st, stats, name = _gpu(model("auto", 1e-6), flat, th, stats=True)
+    assert name.startswith("pmx_jit_ode_auto_grid")
+    assert (wst == 0).all() and (rst == 0).all() and (st == 0).all()
+    e_auto, e_ros = rel_err_floor(got, want).max(), rel_err_floor(ros, want).max()
+    print("auto", e_auto, "ros2", e_ros, "switched pairs", int((stats[..., 3] > 0).sum()), "of", stats[..., 3].size)
+    em = AssayErrorModels.empty().add(0, AssayErrorModel.additive(ErrorPoly(0.1, 0.1, 0.0, 0.0), 0.0))
+    pop = runtime.DevicePopulation(flat, 0)
+    ll, _ = runtime.loglik(model("auto", 1e-6), pop, em, th)
+    wll, _ = runtime.loglik(fine, pop, em, th)
+    ll, wll = ll.cpu().numpy(), wll.cpu().numpy()
+    print("loglik: largest |auto - dopri5(1e-8)| / (1e-6 + 2e-4 |dopri5|):", float((np.abs(ll - wll) / (1e-6 + 2e-4 * np.abs(wll))).max()))
+    np.testing.assert_allclose(ll, wll, rtol=2e-4, atol=1e-6)
+    assert e_auto <= 2.0 * e_ros
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_support", [40, 4])
+def test_gpu_user_closures_through_the_general_walker(n_support):
+    rng = np.random.default_rng(83)
+    subs = []
+    for i in range(12):
+        b = Subject.builder(f"u{i}").bolus(0.0, float(rng.uniform(100, 500)), 0).infusion(5.0, 200.0, 0, 1.5)
+        if i % 2:
+            b = b.bolus(12.0, float(rng.uniform(50, 200)), 0)
+        for t in sorted(rng.uniform(0.1, 36, 6)):
+            b = b.missing_observation(float(t), 0)
+        subs.append(b.build())
+    # [ka, ke, lag]: ka from calm to stiff
+    th = np.stack([np.exp(rng.uniform(np.log(0.5), np.log(3000.0), n_support)), rng.uniform(0.05, 0.4, n_support),
+                   rng.uniform(0.0, 2.0, n_support)], axis=1)
+    fine = _user_lag("dopri5", 1e-8)
+    flat = fine.flatten(Data(subs))
+    want, wst, _ = _gpu(fine, flat, th)
+    ros, rst, _ = _gpu(_user_lag("ros2", 1e-6), flat, th)
+    got, st, stats, name = _gpu(_user_lag("auto", 1e-6), flat, th, stats=True)
+    assert name == ("pmx_jit_ode_user_auto_grid" if n_support >= 32 else "pmx_jit_ode_user_auto_pair")
+    assert (wst == 0).all() and (rst == 0).all() and (st == 0).all()
+    e_auto, e_ros = rel_err_floor(got, want).max(), rel_err_floor(ros, want).max()
+    print("auto", e_auto, "ros2", e_ros, "switched pairs", int((stats[..., 3] > 0).sum()), "of", stats[..., 3].size)
+    assert e_auto <= 2.0 * e_ros
+    assert (stats[..., 0] > 0).all()
