@@ -22,12 +22,12 @@ $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o: $(CSRC)/build/%.o: $(CSRC)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
 # the C ABI's translation units (pmx_internal.hpp): entry points, device streams, launch path, code-object cache
-APIHDR := $(CSRC)/pmx_internal.hpp $(CSRC)/pmx_jit_cache.hpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_jit.hpp $(DEVHDR)
+APIHDR := $(CSRC)/pmx_internal.hpp $(CSRC)/pmx_jit_cache.hpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_jit.hpp $(CSRC)/pmx_solvers.hpp $(DEVHDR)
 $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(CSRC)/build/pmx_jit_cache.o: $(CSRC)/build/%.o: $(CSRC)/%.cpp $(APIHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -x hip -c $< -o $@
 
-KHDR := $(CSRC)/pmx_lanes.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
+KHDR := $(CSRC)/pmx_lanes.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_solvers.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(KHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@
@@ -52,7 +52,7 @@ $(CSRC)/build/pmx_shard.o: $(CSRC)/pmx_shard.cpp include/pmx.h
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -x hip -c $< -o $@
 
-$(CSRC)/build/pmx_jit.o: $(CSRC)/pmx_jit.cpp $(CSRC)/pmx_jit.hpp $(CSRC)/pmx_jit_cache.hpp $(CSRC)/build/pmx_jit_headers.inc
+$(CSRC)/build/pmx_jit.o: $(CSRC)/pmx_jit.cpp $(CSRC)/pmx_jit.hpp $(CSRC)/pmx_solvers.hpp $(CSRC)/pmx_jit_cache.hpp $(CSRC)/build/pmx_jit_headers.inc
 	$(HIPCC) $(DEVFLAGS) -I$(CSRC)/build -x hip -c $< -o $@
 
 $(LIB): $(OBJ)

@@ -854,7 +854,7 @@ static void rk4_piece(const ctx_t* c, double* x, const double* p, const double* 
 }
 
 /* ---- PMX_SOLVER_DOPRI5: Dormand-Prince 5(4) with step-size control (the build's stand-in for the reference's
- * adaptive diffsol solvers; same rule set as pmx_ode.hpp dopri5_try / dopri5_advance). ---------------------- */
+ * adaptive diffsol solvers; same rule set as pmx_ode.hpp dopri5_try / adaptive_advance). ---------------------- */
 static double dopri5_try(const ctx_t* c, const double* x, const double* p, const double* rate, double t, double h,
                          double* xn) {
   const pmx_model_desc* m = c->m;

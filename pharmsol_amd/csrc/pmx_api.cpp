@@ -17,6 +17,8 @@ thread_local const char* g_kernel_name = "";
 
 int32_t create_user_ode(const pmx_model_desc* d, const char* source, uint32_t fns, pmx_model** out);  // (after check_user_ode)
 
+int32_t spec_solver(const pmx_model_desc* d) { return d->eq_kind == PMX_EQ_ODE ? d->ode_solver : PMX_SOLVER_RK4; }  // (JitSpec::solver)
+
 int ode_nstates(int model) {
   static const int n[PMX_ODE_MODEL_COUNT] = {1, 2, 2, 3, 3, 4, 1};
   return (model >= 0 && model < PMX_ODE_MODEL_COUNT) ? n[model] : -1;
@@ -26,9 +28,28 @@ int ode_nparams(int model) {
   return (model >= 0 && model < PMX_ODE_MODEL_COUNT) ? n[model] : -1;
 }
 
-bool known_ode_solver(int32_t v) {
-  return v == PMX_SOLVER_RK4 || v == PMX_SOLVER_DOPRI5 || v == PMX_SOLVER_ROS2 || v == PMX_SOLVER_RK4_CHECKED ||
-         v == PMX_SOLVER_AUTO;  // (4 is no solver)
+// the numeric part of an ODE descriptor, the same for every pmx_model_create*: step ceiling, solver, its tolerances
+int32_t check_ode_numerics(const pmx_model_desc* d) {
+  if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
+  const pmx::SolverRow* solver = pmx::solver_row(d->ode_solver);
+  if (!solver) return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
+  if (solver->needs_tol && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
+    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
+  return PMX_OK;
+}
+
+// what the translation unit of a general-walker ODE model (pmx_ode.hpp) is generated from
+pmx::JitSpec spec_of(const pmx_model_desc* d, const char* source, int32_t has_init) {
+  pmx::JitSpec sp;
+  sp.nstates = d->nstates;
+  sp.nparams = d->nparams;
+  sp.nout = d->nout;
+  sp.ninputs = d->ndrugs > 0 ? d->ndrugs : 1;
+  sp.has_init = has_init != 0;
+  sp.ncov = d->n_covariates;
+  sp.solver = spec_solver(d);
+  sp.source = source;
+  return sp;
 }
 
 // every pmx_model_create* ends here: the model's device-side description is fixed from now on
@@ -268,11 +289,7 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     if (ode_nstates(d->kernel) < 0) return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ODE model");
     if (d->nstates < ode_nstates(d->kernel)) return fail(PMX_ERR_INVALID_ARGUMENT, "model has fewer states than its diffeq");
     if (d->nparams < ode_nparams(d->kernel)) return fail(PMX_ERR_INVALID_ARGUMENT, "too few parameters for the diffeq");
-    if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-    if (!known_ode_solver(d->ode_solver))
-      return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
-    if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-      return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
+    if (const int32_t rc = check_ode_numerics(d); rc != PMX_OK) return rc;
     if (pm) return fail(PMX_ERR_INVALID_ARGUMENT, "pm_* indexing is a wrapper of the analytical structures (analytical/mod.rs:62-90): it does not apply to ODE models");
     if (d->n_bind != 0 && d->n_bind != ode_nparams(d->kernel))
       return fail(PMX_ERR_INVALID_ARGUMENT, "n_bind must equal the diffeq's parameter count");
@@ -338,19 +355,9 @@ int32_t pmx_model_create(const pmx_model_desc* d, pmx_model** out) {
     dd.kernel = PMX_ODE_CUSTOM;
     dd.n_derived = 0;
     dd.n_bind = 0;
-    pmx::JitSpec sp;
-    sp.nstates = d->nstates;
-    sp.nparams = d->nparams;
-    sp.nout = d->nout;
-    sp.ninputs = d->ndrugs > 0 ? d->ndrugs : 1;
-    sp.has_init = m->has_init;
-    sp.ncov = d->n_covariates;
-    sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
-    sp.auto_solver = d->ode_solver == PMX_SOLVER_AUTO;
-    sp.source = pmx::ode_descriptor_source(*d);
     std::string log;
-    m->jit_spec = sp;
-    if (!pmx::jit_compile(sp, &m->jit_code, &log))
+    m->jit_spec = spec_of(d, pmx::ode_descriptor_source(*d).c_str(), m->has_init);
+    if (!pmx::jit_compile(m->jit_spec, &m->jit_code, &log))
       return fail(PMX_ERR_HIP, "hiprtc could not compile the generated diffeq body:\n" + log);
     m->d = dd;
     m->custom = true;
@@ -369,11 +376,7 @@ int32_t check_custom_desc(const pmx_model_desc* d, const char* source) {
   if (d->ndrugs < 0 || d->ndrugs > PMX_MAX_INPUTS) return fail(PMX_ERR_INVALID_ARGUMENT, "ndrugs out of range");
   if (d->nout < 1 || d->nout > PMX_MAX_OUT) return fail(PMX_ERR_INVALID_ARGUMENT, "nout out of range");
   if (d->nparams < 1 || d->nparams > PMX_MAX_PARAMS) return fail(PMX_ERR_INVALID_ARGUMENT, "nparams out of range");
-  if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-  if (!known_ode_solver(d->ode_solver))
-    return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
-  if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
+  if (const int32_t rc = check_ode_numerics(d); rc != PMX_OK) return rc;
   if (d->n_covariates < 0 || d->n_covariates > PMX_MAX_COVARIATES)
     return fail(PMX_ERR_INVALID_ARGUMENT, "n_covariates out of range");
   if (d->n_derived != 0 || d->n_bind != 0 || d->pmetrics_indexing)
@@ -387,19 +390,6 @@ int32_t check_custom_desc(const pmx_model_desc* d, const char* source) {
   }
   (void)n_lag;  // (more than four lagged inputs: pmx_model_create_custom hands the model to the general ODE walker)
   return PMX_OK;
-}
-pmx::JitSpec spec_of(const pmx_model_desc* d, const char* source, int32_t has_init) {
-  pmx::JitSpec sp;
-  sp.nstates = d->nstates;
-  sp.nparams = d->nparams;
-  sp.nout = d->nout;
-  sp.ninputs = d->ndrugs > 0 ? d->ndrugs : 1;
-  sp.has_init = has_init != 0;
-  sp.ncov = d->n_covariates;
-  sp.checked = d->ode_solver == PMX_SOLVER_RK4_CHECKED;
-  sp.auto_solver = d->ode_solver == PMX_SOLVER_AUTO;
-  sp.source = source;
-  return sp;
 }
 }  // namespace
 
@@ -509,10 +499,7 @@ int32_t check_user_ode(const pmx_model_desc* d, const char* source, uint32_t fns
   if (d->n_derived < 0 || d->n_derived > PMX_MAX_USER_DERIVED) return fail(PMX_ERR_INVALID_ARGUMENT, "n_derived out of range");
   if (d->n_derived > 0 && !(fns & PMX_FN_DERIVE)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_derived > 0 needs PMX_FN_DERIVE (desc.derived[] is not read for user models)");
   if (d->n_bind != 0 || d->pmetrics_indexing) return fail(PMX_ERR_INVALID_ARGUMENT, "bind[] / pm indexing do not apply to ODE models with user closures");
-  if (!(d->rk4_h_max > 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "rk4_h_max must be > 0");
-  if (!known_ode_solver(d->ode_solver)) return fail(PMX_ERR_INVALID_ARGUMENT, "unknown ode_solver");
-  if (d->ode_solver != PMX_SOLVER_RK4 && !(d->ode_rtol > 0.0 && d->ode_atol > 0.0))
-    return fail(PMX_ERR_INVALID_ARGUMENT, "the adaptive solvers and checked RK4 need ode_rtol > 0 and ode_atol > 0");
+  if (const int32_t rc = check_ode_numerics(d); rc != PMX_OK) return rc;
   for (int i = 0; i < PMX_MAX_INPUTS; ++i) {
     if (d->lag_param[i] >= d->nparams || d->fa_param[i] >= d->nparams)
       return fail(PMX_ERR_INVALID_ARGUMENT, "lag_param / fa_param out of range");
@@ -528,8 +515,7 @@ pmx::JitSpec user_spec_of(const pmx_model_desc* d, const char* source, uint32_t 
   sp.ode_user = d->eq_kind == PMX_EQ_ODE;
   sp.fns = fns;
   sp.desc = *d;
-  sp.checked = sp.ode_user && d->ode_solver == PMX_SOLVER_RK4_CHECKED;
-  sp.auto_solver = sp.ode_user && d->ode_solver == PMX_SOLVER_AUTO;
+  sp.solver = spec_solver(d);
   sp.source = source;
   return sp;
 }

@@ -89,6 +89,10 @@ struct DevModel {
                                       // PMX_SOLVER_AUTO kernels only.
 };
 constexpr int kMaxLagSlots = 4;
+
+// Which stepper an ODE walker is instantiated with (compile-time: a run-time switch between them costs the fixed-step
+// kernels their registers).  The host maps PMX_SOLVER_* to these (pmx_solvers.hpp); hiprtc sources spell them.
+enum : int { SOLV_RK4 = 0, SOLV_ADAPT = 1, SOLV_CHECKED = 2, SOLV_AUTO = 3 };
 // closure walkers (pmx_userlag.hpp): lagged boluses of one occasion whose landing times a lane keeps sorted in a private
 // array; an occasion with more takes the model's PMX_USER_BIG_LISTS build (compiled on demand, pmx_launch.cpp)
 #ifndef PMX_USER_LAG_KEPT

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pmx.h"
+#include "pmx_solvers.hpp"
 
 namespace pmx {
 
@@ -23,11 +24,9 @@ struct JitSpec {
   bool ode_user = false;
   uint32_t fns = 0;
   pmx_model_desc desc{};
-  // ODE models of PMX_SOLVER_RK4_CHECKED: the translation unit holds the checked-RK4 entry points INSTEAD of the
-  // fixed-step and adaptive ones (a model's solver is fixed at creation), so every other model compiles what it always did
-  bool checked = false;
-  // ... and of PMX_SOLVER_AUTO likewise: the auto entry points instead of the others
-  bool auto_solver = false;
+  // ODE models: the descriptor's ode_solver (a PMX_SOLVER_* value); decides which walkers the translation unit holds
+  // (jit_solv_range, pmx_solvers.hpp)
+  int32_t solver = PMX_SOLVER_RK4;
   bool big_lists = false;  // closure walkers: compile the > 64-boluses-per-occasion path in (PMX_USER_BIG_LISTS, pmx_userlag.hpp)
 };
 enum JitKind { JIT_ODE = 0, JIT_ANALYTICAL = 1, JIT_ODE_USER = 2 };
@@ -35,8 +34,8 @@ inline JitKind jit_kind(const JitSpec& s) { return s.analytical ? JIT_ANALYTICAL
 
 // The translation unit handed to hiprtc (user source + policy + the kernel wrappers: 16 for an ODE model - GRID/PAIR x
 // lag x log-likelihood x solver -, 4 for an analytical one - GRID/PAIR x log-likelihood -, 8 for an ODE model with
-// user lag / fa closures - GRID/PAIR x log-likelihood x solver).  A checked-RK4 model (JitSpec::checked) has the one
-// solver: 8 and 4 wrappers; so has an auto model (JitSpec::auto_solver).
+// user lag / fa closures - GRID/PAIR x log-likelihood x solver).  "solver" = the SOLV_* variants of jit_solv_range(spec.solver):
+// two for a fixed-step or adaptive model, one (8 and 4 wrappers) for a checked-RK4 or an auto model.
 std::string jit_translation_unit(const JitSpec& spec);
 
 // Source text (pmx_derive) of an ANALYTICAL descriptor's derived values (desc.derived[]: theta * covariate factors), for
@@ -55,12 +54,10 @@ bool jit_compile(const JitSpec& spec, std::vector<char>* code, std::string* log)
 
 struct JitModule {
   hipModule_t module = nullptr;
-  hipFunction_t fn[2][2][2][4] = {};  // [mode: 0 GRID, 1 PAIR][LAG][LL][solver: 0 RK4, 1 adaptive, 2 checked RK4, 3 auto]
+  hipFunction_t fn[2][2][2][SOLV_AUTO + 1] = {};  // [mode: 0 GRID, 1 PAIR][LAG][LL][SOLV_*]
 };
-// Load a compiled code object on the CURRENT device and resolve the kernel entry points (`checked`: JitSpec::checked,
-// `auto_solver`: JitSpec::auto_solver).
-hipError_t jit_load(const std::vector<char>& code, JitModule* out, JitKind kind = JIT_ODE, bool checked = false,
-                    bool auto_solver = false);
+// Load a compiled code object on the CURRENT device and resolve the entry points the translation unit of `spec` holds.
+hipError_t jit_load(const std::vector<char>& code, JitModule* out, const JitSpec& spec);
 void jit_unload(JitModule* m);
 
 }  // namespace pmx

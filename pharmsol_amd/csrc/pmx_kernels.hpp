@@ -8,6 +8,7 @@
 
 #include "pmx_compile.hpp"
 #include "pmx_devtypes.hpp"
+#include "pmx_solvers.hpp"
 
 namespace pmx {
 
@@ -82,7 +83,7 @@ struct Route {
   bool lag, dyn;    // lagged input / kernel parameters depend on covariates (re-prepare per PROP)
   bool eig_reuse;   // dyn3: the stream marks segments that repeat the previous built segment's rate constants (EIGR)
   bool leftover;    // walkers behind a classed launch: the subjects of cls.generic_subjects instead of 0..S-1
-  int32_t solver;   // ODE: 0 = RK4, 1 = DOPRI5, 2 = ROS2, 3 = checked RK4, 4 = auto (PMX_SOLVER_AUTO = 5)
+  int32_t solver;   // ODE: index of the solver's row in kSolvers (pmx_solvers.hpp)
   int64_t n;        // walkers: subjects walked; classed: chunks served
   int32_t s_chunk;  // GRID walkers: subjects walked by one block
   int32_t n_ptiles; // GRID: ceil(P / threads)
@@ -159,7 +160,8 @@ hipError_t launch_ode(const LaunchArgs& a, const Route& r);  // (r.mode: grid / 
 hipError_t launch_route(const LaunchArgs& a, const Route& r);
 
 // Run-time flags -> template arguments: dispatch(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), so a launch
-// is written once for all its variants.  with_kid does the same for the analytical kernel id (an unknown one: error).
+// is written once for all its variants.  with_kid does the same for the analytical kernel id (an unknown one: error),
+// with_solv for the ODE walkers' stepper (SOLV_*).
 template <class F>
 hipError_t dispatch(F&& f) {
   return f();
@@ -173,6 +175,14 @@ template <int K = 0, class F>
 hipError_t with_kid(int32_t kernel, F&& f) {
   if constexpr (K < 12) {
     return kernel == K ? f(std::integral_constant<int, K>{}) : with_kid<K + 1>(kernel, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template <int V = SOLV_AUTO, class F>
+hipError_t with_solv(int32_t solv, F&& f) {
+  if constexpr (V >= 0) {
+    return solv == V ? f(std::integral_constant<int, V>{}) : with_solv<V - 1>(solv, f);
   } else {
     return hipErrorInvalidValue;
   }

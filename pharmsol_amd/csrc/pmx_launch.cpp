@@ -172,10 +172,8 @@ pmx::CompileKey key_for(const pmx_model* m, const Tunables& tun, bool has_infusi
     k.rate_input = 0;
     for (int i = 0; i < PMX_MAX_INPUTS; ++i)
       if (m->d.lag_param[i] >= 0) k.lag_mask |= (1u << i);
-    // absolute piece times: a user body may be non-autonomous; the adaptive solvers (auto is one: its stream is
-    // dopri5's) step on [t0, t1] themselves (checked RK4 walks the fixed-step stream as it is)
-    k.want_times = m->custom || m->d.ode_solver == PMX_SOLVER_DOPRI5 || m->d.ode_solver == PMX_SOLVER_ROS2 ||
-                   m->d.ode_solver == PMX_SOLVER_AUTO;
+    // absolute piece times: a user body may be non-autonomous; the adaptive solvers step on [t0, t1] themselves
+    k.want_times = m->custom || pmx::solver_row(m->d.ode_solver)->want_times;
   }
   return k;
 }
@@ -196,7 +194,7 @@ void finish_model(pmx_model* model) {
   m.rk4_h_max = d.rk4_h_max;
   m.ode_rtol = d.ode_rtol;
   m.ode_atol = d.ode_atol;
-  m.ode_stiff = (d.eq_kind == PMX_EQ_ODE && d.ode_solver == PMX_SOLVER_ROS2) ? 1 : 0;
+  m.ode_stiff = (d.eq_kind == PMX_EQ_ODE && pmx::solver_row(d.ode_solver)->stiff) ? 1 : 0;
   std::memcpy(m.derived, d.derived, sizeof(d.derived));
   std::memcpy(m.bind, d.bind, sizeof(d.bind));
   std::memcpy(m.out, d.out, sizeof(d.out));
@@ -243,26 +241,21 @@ static_launch_t static_launcher() {
   return s_static;
 }
 
-// THE name of a route: every string pmx_last_kernel_name can return is written here.
+// THE name of a route: every string pmx_last_kernel_name can return is written (the ODE ones: put together) here.
 const char* route_name(const Route& r) {
-  static const char* const kSolver[5][2][2] = {
-      {{"pmx_ode_rk4_grid", "pmx_ode_rk4_grid<lag>"}, {"pmx_ode_rk4_pair", "pmx_ode_rk4_pair<lag>"}},
-      {{"pmx_ode_dopri5_grid", "pmx_ode_dopri5_grid<lag>"}, {"pmx_ode_dopri5_pair", "pmx_ode_dopri5_pair<lag>"}},
-      {{"pmx_ode_ros2_grid", "pmx_ode_ros2_grid<lag>"}, {"pmx_ode_ros2_pair", "pmx_ode_ros2_pair<lag>"}},
-      {{"pmx_ode_rk4_checked_grid", "pmx_ode_rk4_checked_grid<lag>"}, {"pmx_ode_rk4_checked_pair", "pmx_ode_rk4_checked_pair<lag>"}},
-      {{"pmx_ode_auto_grid", "pmx_ode_auto_grid<lag>"}, {"pmx_ode_auto_pair", "pmx_ode_auto_pair<lag>"}}};
-  static const char* const kJit[5][2][2] = {
-      {{"pmx_jit_ode_rk4_grid", "pmx_jit_ode_rk4_grid<lag>"}, {"pmx_jit_ode_rk4_pair", "pmx_jit_ode_rk4_pair<lag>"}},
-      {{"pmx_jit_ode_dopri5_grid", "pmx_jit_ode_dopri5_grid<lag>"}, {"pmx_jit_ode_dopri5_pair", "pmx_jit_ode_dopri5_pair<lag>"}},
-      {{"pmx_jit_ode_ros2_grid", "pmx_jit_ode_ros2_grid<lag>"}, {"pmx_jit_ode_ros2_pair", "pmx_jit_ode_ros2_pair<lag>"}},
-      {{"pmx_jit_ode_rk4_checked_grid", "pmx_jit_ode_rk4_checked_grid<lag>"},
-       {"pmx_jit_ode_rk4_checked_pair", "pmx_jit_ode_rk4_checked_pair<lag>"}},
-      {{"pmx_jit_ode_auto_grid", "pmx_jit_ode_auto_grid<lag>"}, {"pmx_jit_ode_auto_pair", "pmx_jit_ode_auto_pair<lag>"}}};
-  static const char* const kUser[5][2] = {{"pmx_jit_ode_user_rk4_grid", "pmx_jit_ode_user_rk4_pair"},
-                                          {"pmx_jit_ode_user_dopri5_grid", "pmx_jit_ode_user_dopri5_pair"},
-                                          {"pmx_jit_ode_user_ros2_grid", "pmx_jit_ode_user_ros2_pair"},
-                                          {"pmx_jit_ode_user_rk4_checked_grid", "pmx_jit_ode_user_rk4_checked_pair"},
-                                          {"pmx_jit_ode_user_auto_grid", "pmx_jit_ode_user_auto_pair"}};
+  // the ODE names, built once from the solver table's fragments: pmx_ode_rk4_grid, pmx_jit_ode_auto_pair<lag>, ...
+  struct OdeNames {
+    std::string s[3][pmx::kNumSolvers][2][2];  // [built-in | run-time-compiled | ... with user closures][row][pair][lag]
+    OdeNames() {
+      static const char* const kPrefix[3] = {"pmx_ode_", "pmx_jit_ode_", "pmx_jit_ode_user_"};
+      for (int f = 0; f < 3; ++f)
+        for (int i = 0; i < pmx::kNumSolvers; ++i)
+          for (int pair = 0; pair < 2; ++pair)
+            for (int lag = 0; lag < 2; ++lag)
+              s[f][i][pair][lag] = std::string(kPrefix[f]) + pmx::kSolvers[i].name + (pair ? "_pair" : "_grid") + (lag ? "<lag>" : "");
+    }
+  };
+  static const OdeNames kOde;
   const int pair = r.mode == pmx::MODE_PAIR ? 1 : 0;
   switch (r.family) {
     case pmx::R_CLASSED:
@@ -275,9 +268,9 @@ const char* route_name(const Route& r) {
     case pmx::R_DYN3: return "pmx_analytical_dyn3";
     case pmx::R_GRID: return r.dyn ? "pmx_analytical_grid<dyn>" : (r.lag ? "pmx_analytical_grid<lag>" : "pmx_analytical_grid");
     case pmx::R_PAIR: return r.dyn ? "pmx_analytical_pair<dyn>" : (r.lag ? "pmx_analytical_pair<lag>" : "pmx_analytical_pair");
-    case pmx::R_ODE: return kSolver[r.solver][pair][r.lag ? 1 : 0];
-    case pmx::R_JIT_ODE: return kJit[r.solver][pair][r.lag ? 1 : 0];
-    case pmx::R_JIT_ODE_USER: return kUser[r.solver][pair];
+    case pmx::R_ODE: return kOde.s[0][r.solver][pair][r.lag ? 1 : 0].c_str();
+    case pmx::R_JIT_ODE: return kOde.s[1][r.solver][pair][r.lag ? 1 : 0].c_str();
+    case pmx::R_JIT_ODE_USER: return kOde.s[2][r.solver][pair][0].c_str();
     case pmx::R_JIT_ANALYTICAL: return pair ? "pmx_jit_analytical_pair" : "pmx_jit_analytical_grid";
     case pmx::R_STATIC_AGRID: return "pmx_static_agrid";
   }
@@ -401,12 +394,7 @@ Routes plan_routes(const pmx_model& model, const StreamFacts& f, const Call& c, 
   r.n = c.S;
   out.mode = r.mode;
   if (!analytical || model.custom) {
-    // (Route::solver: the PMX_SOLVER_* values are the route's solver indices, except that PMX_SOLVER_AUTO = 5 - the value
-    // 4 stays refused - takes row 4)
-    static_assert(PMX_SOLVER_RK4 == 0 && PMX_SOLVER_DOPRI5 == 1 && PMX_SOLVER_ROS2 == 2 && PMX_SOLVER_RK4_CHECKED == 3 &&
-                      PMX_SOLVER_AUTO == 5,
-                  "route_name");
-    r.solver = analytical ? 0 : (d.ode_solver == PMX_SOLVER_AUTO ? 4 : d.ode_solver);
+    r.solver = analytical ? 0 : static_cast<int32_t>(pmx::solver_row(d.ode_solver) - pmx::kSolvers);
     r.lag = !analytical && !model.user_ode && model.dev.n_lag_slots > 0;
     r.family = !model.custom ? pmx::R_ODE : (analytical ? pmx::R_JIT_ANALYTICAL : (model.user_ode ? pmx::R_JIT_ODE_USER : pmx::R_JIT_ODE));
     if (model.custom && static_launcher() && r.mode == pmx::MODE_GRID && !c.ll) r.family = pmx::R_STATIC_AGRID;
@@ -468,8 +456,7 @@ int32_t jit_module(const pmx_model* model, const pmx_population* pop, const Devi
   auto it = modules.find(pop->device);
   if (it == modules.end()) {
     pmx::JitModule mod;
-    const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod, pmx::jit_kind(model->jit_spec),
-                                        model->jit_spec.checked, model->jit_spec.auto_solver);
+    const hipError_t le = pmx::jit_load(big ? model->jit_code_big : model->jit_code, &mod, model->jit_spec);
     if (le != hipSuccess) return fail(PMX_ERR_HIP, std::string("loading the compiled model: ") + hipGetErrorString(le));
     it = modules.emplace(pop->device, mod).first;
   }
@@ -483,8 +470,8 @@ int32_t launch_jit(const pmx_model* model, const pmx_population* pop, const Devi
   const pmx::JitModule* jm = nullptr;
   const int32_t rc = jit_module(model, pop, ds, &jm);
   if (rc != PMX_OK) return rc;
-  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][solver]; solver: 0 RK4, 1 adaptive, 2 checked RK4, 3 auto
-  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = r.solver == 4 ? 3 : (r.solver == 3 ? 2 : (r.solver != 0 ? 1 : 0));
+  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][SOLV_*]
+  const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = pmx::kSolvers[r.solver].solv;
   int32_t s_chunk = r.s_chunk, n_ptiles = r.n_ptiles;
   if (r.family == pmx::R_STATIC_AGRID) {
     const int rc_s = static_launcher()(&a.m, &a.ops, a.theta, a.P, a.S, s_chunk, n_ptiles, a.pred, a.ld, a.status,

@@ -66,10 +66,6 @@ __device__ __forceinline__ void rk4_step(const OdeLane<M>& L, double (&x)[M::NS]
   for (int i = 0; i < NS; ++i) x[i] = x[i] + (h / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
 }
 
-// Which stepper a walker is instantiated with (compile-time: a run-time switch between them costs the fixed-step
-// kernels their registers).
-enum : int { SOLV_RK4 = 0, SOLV_ADAPT = 1, SOLV_CHECKED = 2, SOLV_AUTO = 3 };
-
 // ---- adaptive: Dormand-Prince 5(4) ("dopri5" / ode45), PMX_SOLVER_DOPRI5 --------------------------------------
 // One ATTEMPTED step of length h from (t, x): fills xn with the 5th-order solution and returns the scaled error
 // norm rms(e_i / (atol + rtol max(|x_i|, |xn_i|))); the step is acceptable iff the result is <= 1.
@@ -281,47 +277,9 @@ __device__ __forceinline__ void rk4_probe_step(const DevModel& m, const OdeLane<
   if (!(q <= 1.0)) as.failed = 1;  // (also NaN)
 }
 
-// One attempt inside the piece [.., t1]: tries min(h, t1 - t, h_max); on acceptance advances (t, x).  Returns true
-// while the piece is unfinished.  A step that underflows (h < 1e-13 max(1,|t|)) marks the lane failed and jumps to
-// the end of the piece so that every lane terminates.
-template <class M>
-__device__ __forceinline__ bool dopri5_advance(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
-                                               const double (&rs)[M::NR], double& t, double t1, AdaptState& as) {
-  constexpr int NS = M::NS;
-  const double left = t1 - t;
-  if (!(left > 0.0)) return false;
-  double h = fmin(as.h, m.rk4_h_max);
-  const bool clipped = h >= left;
-  if (clipped) h = left;
-  double xn[NS];
-  const bool stiff = m.ode_stiff != 0;  // (wave-uniform: PMX_SOLVER_ROS2)
-  const double err = stiff ? ros2_try<M>(m, L, x, rs, t, h, xn) : dopri5_try<M>(m, L, x, rs, t, h, xn);
-  const bool ok = err <= 1.0;  // (false for NaN)
-  // factor 0.9 err^(-1/(p+1)) in [0.2, 5], p = the order of the error estimate (4 | 1); no growth right after a rejection
-  double fac = (err > 0.0) ? 0.9 * pow(err, stiff ? -0.5 : -0.2) : 5.0;
-  if (!(fac >= 0.2)) fac = 0.2;  // also catches NaN
-  if (fac > 5.0) fac = 5.0;
-  if (!ok && fac > 1.0) fac = 1.0;
-  const double h_next = h * fac;
-  if (ok) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) x[i] = xn[i];
-    t = clipped ? t1 : (t + h);
-    as.h = clipped ? fmax(as.h, h_next) : h_next;  // a step cut short by the piece end must not shrink the proposal
-    return !clipped;
-  }
-  as.h = h_next;
-  if (!(h_next > 1.0e-13 * fmax(1.0, fabs(t)))) {  // step-size underflow (or NaN): give up on this piece
-    as.failed = 1;
-    t = t1;
-    return false;
-  }
-  return true;
-}
-
 // ---- auto: DOPRI5 that moves a stiff lane to ROS2 and back, PMX_SOLVER_AUTO ------------------------------------------
-// The step controller of dopri5_advance (clipping, factor clamps, no growth after a rejection, underflow); the try and
-// the error exponent follow the LANE's mode, so a wave that holds both modes runs both tries under exec masks.
+// The step controller below with AUTO set: the try and the error exponent follow the LANE's mode, so a wave that holds
+// both modes runs both tries under exec masks.
 //   explicit, after an accepted step: Hairer's test of dopri5.f, h rho = h sqrt(sum (k7 - k6)^2 / sum (xn - g6)^2)
 //     (a zero denominator - a state at rest - moves no counter).  h rho > kAutoStiffRho: calm = 0, and the
 //     kAutoStiffSteps-th such step in a row switches to implicit; otherwise ++calm, and calm == kAutoCalmSteps forgets
@@ -329,7 +287,7 @@ __device__ __forceinline__ bool dopri5_advance(const DevModel& m, const OdeLane<
 //   implicit, after an accepted step: h ||J||_inf <= kAutoBackRho (rho <= ||J||_inf: DOPRI5 is inside its stability
 //     interval at this step, and of fifth order where ROS2 is of second) kAutoBackSteps times in a row switches back.
 // A switch keeps (t, x) and the step proposal and zeroes the three counters.
-// One thing beyond dopri5_advance's clipping: a step also ends at the next covariate knot (auto_next_knot), so a lane of
+// One thing beyond the plain controller's clipping: a step also ends at the next covariate knot (auto_next_knot), so a lane of
 // a model WITH interpolated covariates does not walk plain DOPRI5's steps; without covariates it does, to the bit.
 constexpr double kAutoStiffRho = 3.25;  // Hairer
 constexpr int kAutoStiffSteps = 15;     // Hairer
@@ -337,8 +295,8 @@ constexpr int kAutoCalmSteps = 6;       // Hairer
 constexpr double kAutoBackRho = 1.0;    // (this project's: profiles/auto_solver.txt)
 constexpr int kAutoBackSteps = 6;       // (this project's)
 // The next knot of any covariate of the lane's occasion in (t, t1), or t1: segment ends of the interpolation
-// (Covariate::interpolate: a kink where two linear segments meet, a jump at a carry-forward segment).  auto_advance ends
-// its step there.  A stiff lane that has come back to DOPRI5 after its fast component died steps hours at a time, and the
+// (Covariate::interpolate: a kink where two linear segments meet, a jump at a carry-forward segment).  The controller ends
+// an AUTO step there.  A stiff lane that has come back to DOPRI5 after its fast component died steps hours at a time, and the
 // embedded estimate of a step that straddles a kink does not see it (7.8e-5 at tolerances 1e-6 on the covariate fixture
 // of tests/test_auto_solver.py); plain DOPRI5 on such a lane never gets there, stability holds its step at 3.3 / |lambda|.
 template <class M>
@@ -365,25 +323,34 @@ __device__ __forceinline__ double auto_next_knot(const OdeLane<M>& L, double t, 
   return nxt;
 }
 
-template <class M>
-__device__ __forceinline__ bool auto_advance(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
-                                             const double (&rs)[M::NR], double& t, double t1, AdaptState& as) {
+// THE step controller of the adaptive solvers.  One attempt inside the piece [.., t1]: tries min(h, t_end - t, h_max),
+// t_end = t1 (AUTO: the next covariate knot, if one comes first); on acceptance advances (t, x).  Returns true while the
+// piece is unfinished.  A step that underflows (h < 1e-13 max(1,|t|)) marks the lane failed and jumps to the end of the
+// piece so that every lane terminates.  AUTO (PMX_SOLVER_AUTO): the try is the lane's and feeds the switching rule above.
+template <class M, bool AUTO>
+__device__ __forceinline__ bool adaptive_advance(const DevModel& m, const OdeLane<M>& L, double (&x)[M::NS],
+                                                 const double (&rs)[M::NR], double& t, double t1, AdaptState& as) {
   constexpr int NS = M::NS;
   if (!(t1 - t > 0.0)) return false;
-  const double t_end = auto_next_knot<M>(L, t, t1);  // (t1 for a model without covariates)
+  double t_end = t1;
+  if constexpr (AUTO) t_end = auto_next_knot<M>(L, t, t1);  // (t1 for a model without covariates)
   const double left = t_end - t;
   double h = fmin(as.h, m.rk4_h_max);
   const bool clipped = h >= left;
   if (clipped) h = left;
   double xn[NS];
-  const bool stiff = as.implicit != 0;  // (per lane)
-  double aux[2] = {0.0, 0.0};
+  bool stiff;
+  [[maybe_unused]] double aux[2] = {0.0, 0.0};
   double err;
-  if (stiff)
-    err = ros2_try<M, true>(m, L, x, rs, t, h, xn, aux);
-  else
-    err = dopri5_try<M, true>(m, L, x, rs, t, h, xn, aux);
+  if constexpr (AUTO) {
+    stiff = as.implicit != 0;  // (per lane)
+    err = stiff ? ros2_try<M, true>(m, L, x, rs, t, h, xn, aux) : dopri5_try<M, true>(m, L, x, rs, t, h, xn, aux);
+  } else {
+    stiff = m.ode_stiff != 0;  // (wave-uniform: PMX_SOLVER_ROS2)
+    err = stiff ? ros2_try<M>(m, L, x, rs, t, h, xn) : dopri5_try<M>(m, L, x, rs, t, h, xn);
+  }
   const bool ok = err <= 1.0;  // (false for NaN)
+  // factor 0.9 err^(-1/(p+1)) in [0.2, 5], p = the order of the error estimate (4 | 1); no growth right after a rejection
   double fac = (err > 0.0) ? 0.9 * pow(err, stiff ? -0.5 : -0.2) : 5.0;
   if (!(fac >= 0.2)) fac = 0.2;  // also catches NaN
   if (fac > 5.0) fac = 5.0;
@@ -393,34 +360,38 @@ __device__ __forceinline__ bool auto_advance(const DevModel& m, const OdeLane<M>
 #pragma unroll
     for (int i = 0; i < NS; ++i) x[i] = xn[i];
     t = clipped ? t_end : (t + h);
-    as.h = clipped ? fmax(as.h, h_next) : h_next;
-    bool sw = false;
-    if (stiff) {
-      ++as.n_implicit;
-      if (h * aux[0] <= kAutoBackRho) {
-        if (++as.back == kAutoBackSteps) sw = true;
+    as.h = clipped ? fmax(as.h, h_next) : h_next;  // a step cut short by the piece end must not shrink the proposal
+    if constexpr (AUTO) {
+      bool sw = false;
+      if (stiff) {
+        ++as.n_implicit;
+        if (h * aux[0] <= kAutoBackRho) {
+          if (++as.back == kAutoBackSteps) sw = true;
+        } else {
+          as.back = 0;
+        }
       } else {
-        as.back = 0;
-      }
-    } else {
-      ++as.n_explicit;
-      if (aux[1] > 0.0) {
-        if (h * sqrt(aux[0] / aux[1]) > kAutoStiffRho) {
-          as.calm = 0;
-          if (++as.stiff == kAutoStiffSteps) sw = true;
-        } else if (++as.calm == kAutoCalmSteps) {
-          as.stiff = 0;
+        ++as.n_explicit;
+        if (aux[1] > 0.0) {
+          if (h * sqrt(aux[0] / aux[1]) > kAutoStiffRho) {
+            as.calm = 0;
+            if (++as.stiff == kAutoStiffSteps) sw = true;
+          } else if (++as.calm == kAutoCalmSteps) {
+            as.stiff = 0;
+          }
         }
       }
+      if (sw) {
+        as.implicit = stiff ? 0 : 1;
+        as.stiff = as.calm = as.back = 0;
+        ++as.n_switches;
+      }
+      return !(clipped && t_end >= t1);
+    } else {
+      return !clipped;
     }
-    if (sw) {
-      as.implicit = stiff ? 0 : 1;
-      as.stiff = as.calm = as.back = 0;
-      ++as.n_switches;
-    }
-    return !(clipped && t_end >= t1);
   }
-  ++as.n_rejected;
+  if constexpr (AUTO) ++as.n_rejected;
   as.h = h_next;
   if (!(h_next > 1.0e-13 * fmax(1.0, fabs(t)))) {  // step-size underflow (or NaN): give up on this piece
     as.failed = 1;
@@ -561,15 +532,9 @@ __device__ __forceinline__ void ode_piece(const DevModel& m, const OdeLane<M>& L
                                           const double (&rs)[M::NR], double t0, double t1, AdaptState& as) {
   const double dt = t1 - t0;
   if (!(dt > 0.0)) return;
-  if constexpr (SOLV == SOLV_ADAPT) {
+  if constexpr (SOLV == SOLV_ADAPT || SOLV == SOLV_AUTO) {
     double t = t0;
-    for (int32_t guard = 0; guard < 10000000 && dopri5_advance<M>(m, L, x, rs, t, t1, as); ++guard) {
-    }
-    return;
-  }
-  if constexpr (SOLV == SOLV_AUTO) {
-    double t = t0;
-    for (int32_t guard = 0; guard < 10000000 && auto_advance<M>(m, L, x, rs, t, t1, as); ++guard) {
+    for (int32_t guard = 0; guard < 10000000 && adaptive_advance<M, SOLV == SOLV_AUTO>(m, L, x, rs, t, t1, as); ++guard) {
     }
     return;
   }
@@ -1033,10 +998,8 @@ __device__ __forceinline__ void ode_pair_body(const DevModel& m, const DevOps& o
       // op waits for at most that many steps of its neighbours, not for the longest piece in the wave; the host
       // picks the bound from the batch size (pmx_launch.cpp).
       const int32_t spt = ops.steps_per_trip;
-      if constexpr (AUTO) {
-        for (int32_t j = 0; j < spt && stepping; ++j) stepping = auto_advance<M>(m, L, x, rs, t_run, t_run_end, as);
-      } else if constexpr (ADAPT) {
-        for (int32_t j = 0; j < spt && stepping; ++j) stepping = dopri5_advance<M>(m, L, x, rs, t_run, t_run_end, as);
+      if constexpr (ADAPT) {
+        for (int32_t j = 0; j < spt && stepping; ++j) stepping = adaptive_advance<M, AUTO>(m, L, x, rs, t_run, t_run_end, as);
       } else {
         const int32_t kk = rem < spt ? rem : spt;
         int32_t j = 0;

@@ -114,21 +114,25 @@ __global__ __launch_bounds__(kBlock) void pmx_ode_rk4_pair(DevModel m, DevOps op
 
 template <int MODEL>
 hipError_t launch_ode_m(const LaunchArgs& a, const Route& r) {
-  // (the same instantiation serves both adaptive steppers: DevModel::ode_stiff)
-  return dispatch([&](auto lag, auto ll, auto adapt, auto checked, auto autos, auto pair) {
-    constexpr bool LAG = decltype(lag)::value, LL = decltype(ll)::value;
-    constexpr int SOLV = decltype(autos)::value ? SOLV_AUTO
-                                                : (decltype(checked)::value ? SOLV_CHECKED : (decltype(adapt)::value ? SOLV_ADAPT : SOLV_RK4));
-    hipStream_t st = static_cast<hipStream_t>(a.stream);
-    const dim3 grid(static_cast<uint32_t>(r.blocks)), block(r.threads);
-    if constexpr (!decltype(pair)::value)
-      hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, r.s_chunk,
-                         r.n_ptiles, a.pred, a.ld, a.status);
-    else
-      hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S, a.batch, a.pred,
-                         a.ld, a.status);
-    return hipGetLastError();
-  }, r.lag, r.ll, r.solver == 1 || r.solver == 2, r.solver == 3, r.solver == 4, r.mode != MODE_GRID);
+  // (lag, ll, the stepper counted down, pair: the order this unit has always instantiated its kernels in, so its assembly
+  // compares file against file.  The same instantiation serves both adaptive steppers: DevModel::ode_stiff)
+  return dispatch([&](auto lag, auto ll) {
+    return with_solv(kSolvers[r.solver].solv, [&](auto solv) {
+      return dispatch([&](auto pair) {
+        constexpr bool LAG = decltype(lag)::value, LL = decltype(ll)::value;
+        constexpr int SOLV = decltype(solv)::value;
+        hipStream_t st = static_cast<hipStream_t>(a.stream);
+        const dim3 grid(static_cast<uint32_t>(r.blocks)), block(r.threads);
+        if constexpr (!decltype(pair)::value)
+          hipLaunchKernelGGL((pmx_ode_rk4_grid<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S,
+                             r.s_chunk, r.n_ptiles, a.pred, a.ld, a.status);
+        else
+          hipLaunchKernelGGL((pmx_ode_rk4_pair<MODEL, LAG, LL, SOLV>), grid, block, 0, st, a.m, a.ops, a.theta, a.P, a.S,
+                             a.batch, a.pred, a.ld, a.status);
+        return hipGetLastError();
+      }, r.mode != MODE_GRID);
+    });
+  }, r.lag, r.ll);
 }
 
 }  // namespace

@@ -3,16 +3,17 @@
 (prediction.rs:18-27, subject.rs:140-165), per-subject ``estimate_log_likelihood`` / ``simulate_subject``
 (equation/mod.rs:468-477,569-576), ``log_likelihood_batch`` with prediction-based ``ResidualErrorModels`` and its
 failure -> -inf rule (likelihood/mod.rs:119-177, residual_error.rs:178-271), the host-pointer entry points' persistent
-workspace (pinned or pageable outputs)."""
+workspace (pinned or pageable outputs); what every model-creation path refuses of an ODE descriptor's solver fields."""
+import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
 import oracle
-from pharmsol_amd import (Analytical, AssayErrorModel, AssayErrorModels, Censor, Data, ErrorPoly, ParameterError,
-                          ParameterOrder, Parameters, Ratio, ResidualErrorModel, ResidualErrorModels, Subject, _abi, runtime,
-                          synth)
+from pharmsol_amd import (ODE, Analytical, AssayErrorModel, AssayErrorModels, Censor, Data, ErrorPoly, ParameterError,
+                          ParameterOrder, Parameters, Ratio, ResidualErrorModel, ResidualErrorModels, Subject, _abi, _ffi,
+                          runtime, synth)
 from tests import models
 
 
@@ -193,3 +194,45 @@ def test_host_pointer_entry_points_reuse_their_workspace_and_take_pinned_or_page
     sink = np.empty((NO, 96))
     rc = L.pmx_predict(dm.handle, pop.handle, bad.ctypes.data, 96, sink.ctypes.data, 96, None)
     assert rc == _abi.PMX_ERR_PAIR_FAILED and np.isnan(sink[:, 3]).all() and np.isfinite(np.delete(sink, 3, axis=1)).all()
+
+
+# --------------------------------------------------------------------------- ODE solver fields (no GPU, no compiler)
+_SIG = "double t, const double* x, const double* p, const double* cov, const double* rateiv, const double* derived, double* "
+_ORAL_SRC = (f"PMX_DEVICE void pmx_dynamics({_SIG}dx) {{ dx[0] = -p[0] * x[0]; dx[1] = p[0] * x[0] - p[1] * x[1] + rateiv[0]; }}\n"
+             f"PMX_DEVICE void pmx_outputs({_SIG}y) {{ y[0] = x[1]; }}\n")
+_ORAL_LAG_SRC = _ORAL_SRC + f"PMX_DEVICE void pmx_route_lag({_SIG}lag) {{ lag[0] = p[2]; }}\n"
+
+
+def test_every_creation_path_refuses_unknown_solvers_and_missing_tolerances():
+    """pmx_model_create (built-in diffeq body), pmx_model_create_custom and pmx_model_create_user (ODE descriptor with a
+    lag closure: the general walker's path) check the same three numbers the same way: ode_solver -1, 4 and 6 are no
+    solvers; every solver but plain RK4 needs ode_rtol > 0 and ode_atol > 0.  Each call is refused by the descriptor
+    check, before the source text is looked at."""
+    L = _ffi.lib()
+    builtin = ODE.new("one_cmt_oral", {0: Ratio(1)}, nparams=2, h_max=0.02).with_nstates(2).with_ndrugs(1).with_nout(1)
+    custom = ODE.custom(_ORAL_SRC, nstates=2, nparams=2, h_max=0.02)
+    user = ODE.user(_ORAL_LAG_SRC, nstates=2, nparams=3, ndrugs=1, nout=1, h_max=0.02)
+    assert user.user_fns & _abi.PMX_FN_ROUTE_LAG  # (without a closure beyond the dynamics the call is create_custom's)
+    paths = {
+        "create": lambda d, h: L.pmx_model_create(C.byref(d), C.byref(h)),
+        "create_custom": lambda d, h: L.pmx_model_create_custom(C.byref(d), _ORAL_SRC.encode(), 0, C.byref(h)),
+        "create_user": lambda d, h: L.pmx_model_create_user(C.byref(d), _ORAL_LAG_SRC.encode(), int(user.user_fns), C.byref(h)),
+    }
+    models_ = {"create": builtin, "create_custom": custom, "create_user": user}
+    need_tol = (_abi.PMX_SOLVER_DOPRI5, _abi.PMX_SOLVER_ROS2, _abi.PMX_SOLVER_RK4_CHECKED, _abi.PMX_SOLVER_AUTO)
+
+    def refused(path, **fields):
+        d = models_[path].desc()
+        d.ode_rtol = d.ode_atol = 1e-6
+        for k, v in fields.items():
+            setattr(d, k, v)
+        h = C.c_void_p()
+        rc = paths[path](d, h)
+        assert rc == _abi.PMX_ERR_INVALID_ARGUMENT and not h.value, (path, fields, rc)
+
+    for path in paths:
+        for solver in (-1, 4, 6):
+            refused(path, ode_solver=solver)
+        for solver in need_tol:
+            refused(path, ode_solver=solver, ode_rtol=0.0)
+            refused(path, ode_solver=solver, ode_atol=0.0)

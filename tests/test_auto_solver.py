@@ -1,7 +1,7 @@
 """PMX_SOLVER_AUTO (``ODE.with_solver("auto")``, alias ``"lsoda"``): DOPRI5 that detects stiffness per lane, moves that
-lane to ROS2 and back (csrc/pmx_ode.hpp auto_advance).  The rule, restated here in numpy:
+lane to ROS2 and back (csrc/pmx_ode.hpp adaptive_advance<M, AUTO = true>).  The rule, restated here in numpy:
 
-  one step controller for both methods (dopri5_advance's: clipping to the piece end and to h_max, factor
+  one step controller for both methods (the adaptive solvers': clipping to the piece end and to h_max, factor
   0.9 err^(-1/5 | -1/2) in [0.2, 5], no growth after a rejection, underflow); try and exponent follow the lane's mode.
   explicit, after an accepted step (Hairer, dopri5.f): h rho = h sqrt(sum (k7 - k6)^2 / sum (xn - g6)^2); a zero
     denominator moves no counter; h rho > 3.25: calm = 0, the 15th such step in a row switches to implicit; otherwise
@@ -391,8 +391,8 @@ def test_gpu_custom_body_with_lag_covariate_and_likelihood():
     The covariate is linear on [0, 24] and constant after: a knot at t = 24.  A stiff lane (ka 50 to 2000) goes implicit
     after the transient, comes back to DOPRI5 when piece ends have cut ROS2's steps short (infusion at 5 h), and - the fast
     component being numerically zero by then - steps 2 to 3 h at a time.  A step that straddles the knot is judged by an
-    embedded estimate that does not see the kink: 7.8e-5 here against ROS2's 1.0e-5 before auto_advance ended its steps
-    at covariate knots (auto_next_knot), 9.2e-6 with it."""
+    embedded estimate that does not see the kink: 7.8e-5 here against ROS2's 1.0e-5 before the controller ended
+    its AUTO steps at covariate knots (auto_next_knot), 9.2e-6 with it."""
     from pharmsol_amd import AssayErrorModel, AssayErrorModels, ErrorPoly
 
     rng = np.random.default_rng(74)
