@@ -12,8 +12,12 @@ lane to ROS2 and back (csrc/pmx_ode.hpp adaptive_advance<M, AUTO = true>).  The 
   a model with interpolated covariates: a step also ends at the next covariate knot (auto_next_knot; none in the
     restatement's autonomous bodies).
 
-Plain f64 without FMA here; the device contracts, so the GPU tests compare through the library (auto against dopri5 /
-ros2 on the same device) and against closed forms, never step for step against this file.  The oracle has no auto mode."""
+Plain f64 without FMA here; the device contracts, so the GPU tests of this file compare through the library (auto against
+dopri5 / ros2 on the same device) and against closed forms.  The switch rule itself - the counts, the mode of every step,
+the statistics of every pair - and both methods' arithmetic are pinned step for step elsewhere: tests/golden/
+ode_exact_stiff.json holds a deterministic switch walked in 40-digit arithmetic (tests/golden/gen_ode_exact_stiff.py);
+`walk` below is held to it in tests/test_oracle_ode_stiff_exact.py, the device in tests/test_gpu_ode_stiff_exact.py.  The
+oracle has no auto mode."""
 import ctypes as C
 
 import numpy as np
@@ -31,54 +35,72 @@ GAMMA = 1.7071067811865475
 SQRT_EPS = 1.4901161193847656e-08
 
 
-def dopri5_try(f, x, h, tol):
-    k1 = f(x)
-    k2 = f(x + h * (0.2 * k1))
-    k3 = f(x + h * ((3.0 / 40.0) * k1 + (9.0 / 40.0) * k2))
-    k4 = f(x + h * ((44.0 / 45.0) * k1 - (56.0 / 15.0) * k2 + (32.0 / 9.0) * k3))
-    k5 = f(x + h * ((19372.0 / 6561.0) * k1 - (25360.0 / 2187.0) * k2 + (64448.0 / 6561.0) * k3 - (212.0 / 729.0) * k4))
+def _timed(f, t):
+    """(F(s, y), t): the right-hand side with a time argument; t = None marks an autonomous f(y)."""
+    return ((lambda s, y: f(y)), 0.0) if t is None else (f, t)
+
+
+def dopri5_try(f, x, h, tol, t=None):
+    f, t = _timed(f, t)
+    k1 = f(t, x)
+    k2 = f(t + 0.2 * h, x + h * (0.2 * k1))
+    k3 = f(t + 0.3 * h, x + h * ((3.0 / 40.0) * k1 + (9.0 / 40.0) * k2))
+    k4 = f(t + 0.8 * h, x + h * ((44.0 / 45.0) * k1 - (56.0 / 15.0) * k2 + (32.0 / 9.0) * k3))
+    k5 = f(t + (8.0 / 9.0) * h,
+           x + h * ((19372.0 / 6561.0) * k1 - (25360.0 / 2187.0) * k2 + (64448.0 / 6561.0) * k3 - (212.0 / 729.0) * k4))
     g6 = x + h * ((9017.0 / 3168.0) * k1 - (355.0 / 33.0) * k2 + (46732.0 / 5247.0) * k3 + (49.0 / 176.0) * k4
                   - (5103.0 / 18656.0) * k5)
-    k6 = f(g6)
+    k6 = f(t + h, g6)
     xn = x + h * ((35.0 / 384.0) * k1 + (500.0 / 1113.0) * k3 + (125.0 / 192.0) * k4 - (2187.0 / 6784.0) * k5
                   + (11.0 / 84.0) * k6)
-    k7 = f(xn)
+    k7 = f(t + h, xn)
     e = h * ((71.0 / 57600.0) * k1 - (71.0 / 16695.0) * k3 + (71.0 / 1920.0) * k4 - (17253.0 / 339200.0) * k5
              + (22.0 / 525.0) * k6 - (1.0 / 40.0) * k7)
     sc = tol + tol * np.maximum(np.abs(x), np.abs(xn))
     return xn, float(np.sqrt(np.mean((e / sc) ** 2))), float(np.sum((k7 - k6) ** 2)), float(np.sum((xn - g6) ** 2))
 
 
-def ros2_try(f, x, h, tol):
-    """(autonomous right-hand sides: the f_t term is exactly zero)"""
+def ros2_try(f, x, h, tol, t=None):
+    """(t = None, an autonomous right-hand side f(y): the f_t term is exactly zero and is left out)"""
+    timed = t is not None
+    f, t = _timed(f, t)
     n = len(x)
     gh = GAMMA * h
-    f0 = f(x)
+    f0 = f(t, x)
     W, rows = np.empty((n, n)), np.zeros(n)
     for j in range(n):
         xt = x.copy()
         d = SQRT_EPS * max(abs(x[j]), 1.0)
         xt[j] = x[j] + d
-        df = f(xt) - f0
+        df = f(t, xt) - f0
         W[:, j] = df * (-gh / d)
         W[j, j] += 1.0
         rows += np.abs(df) / d
-    k1 = np.linalg.solve(W, f0)
-    k2 = np.linalg.solve(W, f(x + h * k1) - 2.0 * k1)
+    ft = 0.0
+    if timed:
+        dt = SQRT_EPS * max(abs(t), 1.0)
+        ft = (f(t + dt, x) - f0) * (gh / dt)
+    k1 = np.linalg.solve(W, f0 + ft)
+    k2 = np.linalg.solve(W, f(t + h, x + h * k1) - ft - 2.0 * k1)
     xn = x + h * (1.5 * k1 + 0.5 * k2)
     e = (0.5 * h) * (k1 + k2)
     sc = tol + tol * np.maximum(np.abs(x), np.abs(xn))
     return xn, float(np.sqrt(np.mean((e / sc) ** 2))), float(rows.max())
 
 
-def walk(f, x0, pieces, tol, h_max, solver):
-    """solver: "dopri5" | "ros2" | "auto".  -> (states at the piece ends, [explicit, implicit, rejected, switches])"""
+def walk(f, x0, pieces, tol, h_max, solver, timed=False, before=None, modes=None):
+    """solver: "dopri5" | "ros2" | "auto".  -> (states at the piece ends, [explicit, implicit, rejected, switches]).
+    timed: the right-hand side is f(t, y) (the stage times and ROS2's f_t term are live).  before(k, x) -> x runs at the
+    start of piece k (a bolus; a closure may change f's rates there).  modes: a list that receives "E" | "I" per
+    accepted step."""
     x, hprop = np.array(x0, dtype=float), h_max
     implicit = solver == "ros2"
     stiff = calm = back = 0
     n_e = n_i = n_r = n_s = 0
     out = []
-    for (t, t1) in pieces:
+    for k, (t, t1) in enumerate(pieces):
+        if before is not None:
+            x = before(k, x)
         while True:
             left = t1 - t
             if not left > 0.0:
@@ -88,9 +110,9 @@ def walk(f, x0, pieces, tol, h_max, solver):
             if clipped:
                 h = left
             if implicit:
-                xn, err, nj = ros2_try(f, x, h, tol)
+                xn, err, nj = ros2_try(f, x, h, tol, t if timed else None)
             else:
-                xn, err, num, den = dopri5_try(f, x, h, tol)
+                xn, err, num, den = dopri5_try(f, x, h, tol, t if timed else None)
             ok = err <= 1.0
             fac = 0.9 * err ** (-0.5 if implicit else -0.2) if err > 0.0 else 5.0
             if not fac >= 0.2:
@@ -107,6 +129,8 @@ def walk(f, x0, pieces, tol, h_max, solver):
                 continue
             x, t = xn, (t1 if clipped else t + h)
             hprop = max(hprop, h_next) if clipped else h_next
+            if modes is not None:
+                modes.append("I" if implicit else "E")
             sw = False
             if implicit:
                 n_i += 1

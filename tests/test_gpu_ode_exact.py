@@ -89,24 +89,27 @@ def population(group, model, n_copies=len(SCALES)):
     return model.flatten(Data(subs)), scales
 
 
-def launch(model, flat, theta, expect, batch=False):
+def launch(model, flat, theta, expect, batch=False, stats=False):
+    """-> (predictions, status); stats (auto solver): also the four step counts per pair, [n_subjects, n, 4]."""
     import torch
 
     pop = runtime.DevicePopulation(flat, 0)
-    pred, status = runtime.predict(model, pop, np.ascontiguousarray(theta), batch=batch)
+    out = runtime.predict(model, pop, np.ascontiguousarray(theta), batch=batch, solver_stats=stats)
     torch.cuda.synchronize()
     name = runtime.last_kernel_name()
     assert name == expect, f"routed to {name}, expected {expect}"
-    return pred.cpu().numpy().reshape(flat.n_observations, -1), status.cpu().numpy().reshape(flat.n_subjects, -1)
+    res = (out[0].cpu().numpy().reshape(flat.n_observations, -1), out[1].cpu().numpy().reshape(flat.n_subjects, -1))
+    return res + ((out[2].cpu().numpy().reshape(flat.n_subjects, -1, 4),) if stats else ())
 
 
-def check(group, model, cases, want, wstatus, bars, idx, expect, batch=False, walker=None, err_fn=None):
+def check(group, model, cases, want, wstatus, bars, idx, expect, batch=False, walker=None, err_fn=None, wstats=None):
     """One launch; idx[k] = the case of support point k (of subject k in a batch).  want [n_obs, n_cases] may hold NaN
-    (rows a checked lane refuses).  Returns the raw predictions."""
+    (rows a checked lane refuses).  wstats (auto solver): the four step counts of every case, which every pair's
+    statistics record must equal.  Returns the raw predictions."""
     n = len(idx)
     flat, scales = population(group, model, n if batch else len(SCALES))
     theta = np.array([cases[i]["theta"] for i in idx])
-    pred, status = launch(model, flat, theta, expect, batch)
+    pred, status, *stats = launch(model, flat, theta, expect, batch, stats=wstats is not None)
     n_obs = want.shape[0]
     walker = walker or expect
     for s, scale in enumerate(scales):
@@ -116,6 +119,8 @@ def check(group, model, cases, want, wstatus, bars, idx, expect, batch=False, wa
             col = 0 if batch else k
             where = f"{group['name']}[{c}] subject {s} P={n}"
             assert status[s, col] == wstatus[c], f"{walker}: {where}: status {status[s, col]}, fixture {wstatus[c]}"
+            if wstats is not None:
+                assert list(stats[0][s, col]) == list(wstats[c]), f"{walker}: {where}: steps {stats[0][s, col]}, fixture {wstats[c]}"
             got, w = rows[:, col], want[:, c] * scale
             bad = np.isnan(w)
             assert np.isnan(got[bad]).all() and np.isfinite(got[~bad]).all(), f"{walker}: {where}: {got}"
@@ -225,12 +230,12 @@ def test_adaptive_solvers_against_the_true_solution(g, solver, env):
 
 
 # ------------------------------------------------------------------------------------------------ fused log-likelihood
-def check_ll(group, model, cases, want, wstatus, bars, idx, expect):
+def check_ll(group, model, cases, want, wstatus, bars, idx, expect, key="rk4"):
     import torch
 
     flat, scales = population(group, model)
     n_obs = want.shape[0]
-    full = np.array([c["rk4"] for c in cases]).T
+    full = np.array([c[key] for c in cases]).T
     rng = np.random.default_rng(5)
     y = [np.abs(full[:, 0] * s) * np.exp(rng.normal(0, 0.2, n_obs)) + 0.05 for s in scales]
     flat.ev_value = flat.ev_value.copy()

@@ -2,7 +2,11 @@
 ``Sdirk``, ode/mod.rs:60-77, which this build replaces: SURVEY.md §8 a23).  An L-stable second-order Rosenbrock method
 with the adaptive step control of the DOPRI5 path (csrc/pmx_ode.hpp ros2_try, oracle/pmx_oracle.c ros2_try).  Pinned by
 the closed forms of the analytical back-end on STIFF parameter sets (absorption / distribution 10^3-10^4 times faster than
-elimination), by fixed-step RK4 on the non-linear body, and - on the GPU - by the oracle's restatement of the same method."""
+elimination), by fixed-step RK4 on the non-linear body, and - on the GPU - by the oracle's restatement of the same method.
+These checks see whether the solver meets its tolerance, not whether a stage is right (ROS2 keeps its order for any matrix
+in the Jacobian's place; the controller shortens the steps): the method's arithmetic - gamma, both stages, the f_t term,
+the elimination up to 8 states - is pinned against 40-digit steps in tests/golden/ode_exact_stiff.json
+(tests/test_oracle_ode_stiff_exact.py, tests/test_gpu_ode_stiff_exact.py)."""
 import numpy as np
 import pytest
 
