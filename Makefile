@@ -9,7 +9,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
 # the kernel units: one translation unit per kernel family (pmx_lanes.hpp lists them)
 KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util
-OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
+OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_model.o $(CSRC)/build/pmx_host.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 
 all: $(LIB) oracle
@@ -23,7 +23,7 @@ $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o: $(CSRC)/build/%.o: $(CSRC)
 
 # the C ABI's translation units (pmx_internal.hpp): entry points, device streams, launch path, code-object cache
 APIHDR := $(CSRC)/pmx_internal.hpp $(CSRC)/pmx_jit_cache.hpp $(CSRC)/pmx_compile.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_jit.hpp $(CSRC)/pmx_solvers.hpp $(DEVHDR)
-$(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(CSRC)/build/pmx_jit_cache.o: $(CSRC)/build/%.o: $(CSRC)/%.cpp $(APIHDR)
+$(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_model.o $(CSRC)/build/pmx_host.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(CSRC)/build/pmx_jit_cache.o: $(CSRC)/build/%.o: $(CSRC)/%.cpp $(APIHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -x hip -c $< -o $@
 

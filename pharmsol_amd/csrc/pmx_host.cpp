@@ -1,0 +1,287 @@
+// pmx_host.cpp — the HOST-pointer entry points of include/pmx.h: pmx_predict, pmx_predict_batch, pmx_loglik,
+// pmx_loglik_batch.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
+// result out.
+#include <cstring>
+#include <limits>
+
+#include "pmx_internal.hpp"
+
+// What they keep between calls, per population: device buffers for theta / output / status (grown, never shrunk), a private stream pair and
+// two pinned bounce buffers.  An NPAG loop calls these entry points thousands of times; allocating, page-locking and
+// freeing per call cost ~700x the kernel (profiles/r01/pcie_inclusive.txt).  Calls on one population take turns.
+struct HostWorkspace {
+  std::mutex mu;
+  hipStream_t compute = nullptr, copy = nullptr;
+  void* d_theta = nullptr;
+  void* d_out = nullptr;
+  void* d_status = nullptr;
+  int32_t* d_flag = nullptr;  // "any pair failed" (pmx_status_any)
+  size_t theta_cap = 0, out_cap = 0, status_cap = 0;
+  static constexpr size_t kBounce = 32u << 20;
+  void* bounce[2] = {nullptr, nullptr};
+  hipEvent_t bev[2] = {nullptr, nullptr};
+  int32_t* h_flag = nullptr;  // pinned
+  ~HostWorkspace() {
+    if (d_theta) (void)hipFree(d_theta);
+    if (d_out) (void)hipFree(d_out);
+    if (d_status) (void)hipFree(d_status);
+    if (d_flag) (void)hipFree(d_flag);
+    for (int i = 0; i < 2; ++i) {
+      if (bounce[i]) (void)hipHostFree(bounce[i]);
+      if (bev[i]) (void)hipEventDestroy(bev[i]);
+    }
+    if (h_flag) (void)hipHostFree(h_flag);
+    if (compute) (void)hipStreamDestroy(compute);
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+
+pmx_population::pmx_population() = default;
+pmx_population::~pmx_population() {
+  for (void* p : ll_allocs) (void)hipFree(p);
+}
+
+extern "C" void pmx_population_destroy(pmx_population* pop) {
+  if (!pop) return;
+  {
+    DeviceGuard g;
+    (void)g.enter(pop->device);
+    pop->streams.clear();
+    pop->ws.reset();
+  }
+  delete pop;
+}
+
+namespace {
+
+int32_t ws_get(pmx_population* pop, HostWorkspace** out) {
+  std::lock_guard<std::mutex> lock(pop->mu);
+  if (!pop->ws) {
+    auto ws = std::make_unique<HostWorkspace>();
+    PMX_HIP(hipStreamCreateWithFlags(&ws->compute, hipStreamNonBlocking));
+    PMX_HIP(hipStreamCreateWithFlags(&ws->copy, hipStreamNonBlocking));
+    PMX_HIP(hipMalloc(reinterpret_cast<void**>(&ws->d_flag), sizeof(int32_t)));
+    PMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_flag), sizeof(int32_t), hipHostMallocDefault));
+    for (int i = 0; i < 2; ++i) {
+      PMX_HIP(hipHostMalloc(&ws->bounce[i], HostWorkspace::kBounce, hipHostMallocDefault));
+      PMX_HIP(hipEventCreateWithFlags(&ws->bev[i], hipEventDisableTiming));
+    }
+    pop->ws = std::move(ws);
+  }
+  *out = pop->ws.get();
+  return PMX_OK;
+}
+
+int32_t ws_reserve(void** p, size_t* cap, size_t need) {
+  if (need <= *cap && *p) return PMX_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need > 0 ? ((need + (1u << 20) - 1) >> 20) << 20 : (1u << 20);  // whole MiB
+  PMX_HIP(hipMalloc(p, want));
+  *cap = want;
+  return PMX_OK;
+}
+
+bool is_pinned_host(const void* p) {
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // (an ordinary malloc'ed pointer: "invalid value", not an error of ours)
+    return false;
+  }
+  return a.type == hipMemoryTypeHost;
+}
+
+// rows x row_bytes from a dense device buffer to host rows `dst_pitch` apart, after everything enqueued on ws->compute.
+// Page-locked destinations (pmx_host_alloc, hipHostMalloc, hipHostRegister) take ONE DMA at link rate; pageable ones go
+// through the two pinned bounce buffers, the DMA of one piece overlapping the CPU copy of the previous one.
+int32_t ws_copy_out(HostWorkspace* ws, void* dst, size_t dst_pitch, const void* src, size_t row_bytes, size_t rows) {
+  if (rows == 0 || row_bytes == 0) {
+    PMX_HIP(hipStreamSynchronize(ws->compute));
+    return PMX_OK;
+  }
+  if (is_pinned_host(dst)) {
+    if (dst_pitch == row_bytes)
+      PMX_HIP(hipMemcpyAsync(dst, src, row_bytes * rows, hipMemcpyDeviceToHost, ws->compute));
+    else
+      PMX_HIP(hipMemcpy2DAsync(dst, dst_pitch, src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, ws->compute));
+    PMX_HIP(hipStreamSynchronize(ws->compute));
+    return PMX_OK;
+  }
+  PMX_HIP(hipStreamSynchronize(ws->compute));
+  const size_t total = row_bytes * rows;
+  const size_t piece = HostWorkspace::kBounce;
+  const size_t n_pieces = (total + piece - 1) / piece;
+  auto land = [&](size_t k) {  // bounce[k % 2] -> the caller's rows
+    const size_t off = k * piece, len = (off + piece <= total) ? piece : total - off;
+    const char* b = static_cast<const char*>(ws->bounce[k % 2]);
+    if (dst_pitch == row_bytes) {
+      std::memcpy(static_cast<char*>(dst) + off, b, len);
+      return;
+    }
+    size_t done = 0;
+    while (done < len) {  // split at row ends
+      const size_t at = off + done, r = at / row_bytes, c = at % row_bytes;
+      const size_t n = (row_bytes - c < len - done) ? row_bytes - c : len - done;
+      std::memcpy(static_cast<char*>(dst) + r * dst_pitch + c, b + done, n);
+      done += n;
+    }
+  };
+  for (size_t k = 0; k < n_pieces; ++k) {
+    const size_t off = k * piece, len = (off + piece <= total) ? piece : total - off;
+    PMX_HIP(hipMemcpyAsync(ws->bounce[k % 2], static_cast<const char*>(src) + off, len, hipMemcpyDeviceToHost, ws->copy));
+    PMX_HIP(hipEventRecord(ws->bev[k % 2], ws->copy));
+    if (k > 0) {
+      PMX_HIP(hipEventSynchronize(ws->bev[(k - 1) % 2]));
+      land(k - 1);
+    }
+  }
+  PMX_HIP(hipEventSynchronize(ws->bev[(n_pieces - 1) % 2]));
+  land(n_pieces - 1);
+  return PMX_OK;
+}
+
+// Every exit path of a host-pointer entry point leaves nothing in flight: the caller may free or reuse theta and its
+// (possibly page-locked) outputs as soon as the call returns - also when it returns an error half-way - and the next
+// call reuses the workspace buffers.
+struct WsDrain {
+  HostWorkspace* ws = nullptr;
+  ~WsDrain() {
+    if (!ws) return;
+    (void)hipStreamSynchronize(ws->compute);
+    (void)hipStreamSynchronize(ws->copy);
+  }
+};
+
+// the per-pair status bytes: "did any pair fail" comes back as ONE flag reduced on the device (the array itself is only
+// copied when the caller asked for it: 100 MB for C3)
+int32_t ws_finish_status(HostWorkspace* ws, uint8_t* status, size_t n_status, bool* any_failed) {
+  PMX_HIP(hipMemsetAsync(ws->d_flag, 0, sizeof(int32_t), ws->compute));
+  PMX_HIP(pmx::launch_status_any(static_cast<const uint8_t*>(ws->d_status), static_cast<int64_t>(n_status), ws->d_flag, ws->compute));
+  PMX_HIP(hipMemcpyAsync(ws->h_flag, ws->d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, ws->compute));
+  if (status) {
+    const int32_t rc = ws_copy_out(ws, status, n_status, ws->d_status, n_status, 1);
+    if (rc != PMX_OK) return rc;
+  } else {
+    PMX_HIP(hipStreamSynchronize(ws->compute));
+  }
+  *any_failed = *ws->h_flag != 0;
+  return PMX_OK;
+}
+
+// One host-pointer call: the caller's device, this population's workspace for the length of the call (calls on one
+// population take turns), theta on the device and a zeroed status array - then the kernels, then finish().  The members
+// go in reverse order: drain, end of turn, the caller's device back.
+struct HostCall {
+  DeviceGuard guard;
+  std::unique_lock<std::mutex> turn;
+  WsDrain drain;
+  HostWorkspace* ws = nullptr;
+  int64_t Pd = 1;  // columns of the dense device matrix; the caller's padding columns are never touched
+  size_t n_status = 0, rows = 0;
+  double* d_out() const { return static_cast<double*>(ws->d_out); }
+
+  // out_rows: rows of the result (observations, or subjects); matrix shape [out_rows][P], batch shape [out_rows]
+  int32_t begin(const pmx_model* model, pmx_population* pop, const double* theta, int64_t P, int batch, int64_t out_rows) {
+    PMX_HIP(guard.enter(pop->device));
+    int32_t rc = ws_get(pop, &ws);
+    if (rc != PMX_OK) return rc;
+    turn = std::unique_lock<std::mutex>(ws->mu);
+    drain.ws = ws;
+    const int64_t S = pop->hp.n_subjects;
+    Pd = batch ? 1 : P;
+    rows = static_cast<size_t>(out_rows);
+    n_status = static_cast<size_t>(S * Pd);
+    const size_t theta_bytes = static_cast<size_t>(batch ? S : P) * model->d.nparams * sizeof(double);
+    if ((rc = ws_reserve(&ws->d_theta, &ws->theta_cap, theta_bytes)) != PMX_OK) return rc;
+    if ((rc = ws_reserve(&ws->d_out, &ws->out_cap, rows * Pd * sizeof(double))) != PMX_OK) return rc;
+    if ((rc = ws_reserve(&ws->d_status, &ws->status_cap, n_status)) != PMX_OK) return rc;
+    PMX_HIP(hipMemcpyAsync(ws->d_theta, theta, theta_bytes, hipMemcpyHostToDevice, ws->compute));
+    if (n_status > 0) PMX_HIP(hipMemsetAsync(ws->d_status, 0, n_status, ws->compute));
+    return PMX_OK;
+  }
+  int32_t run(const pmx_model* model, pmx_population* pop, int64_t P, int batch, const LLRequest* req = nullptr) {
+    return enqueue(model, pop, static_cast<const double*>(ws->d_theta), P, batch, d_out(), Pd, static_cast<uint8_t*>(ws->d_status),
+                   ws->compute, req);
+  }
+  // the status flag (and array, if asked for), then the result into the caller's rows `ld` doubles apart
+  int32_t finish(uint8_t* status, double* out, int64_t ld, bool* any_failed) {
+    const int32_t rc = ws_finish_status(ws, status, n_status, any_failed);
+    if (rc != PMX_OK) return rc;
+    return ws_copy_out(ws, out, static_cast<size_t>(ld) * sizeof(double), ws->d_out, static_cast<size_t>(Pd) * sizeof(double), rows);
+  }
+};
+
+constexpr const char* kPairFailed = "at least one (subject, support point) pair failed; see the status array";
+
+int32_t predict_host(const pmx_model* model, const pmx_population* cpop, const double* theta, int64_t P, int batch,
+                     double* pred, int64_t ld, uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !cpop || !theta || !pred) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!batch && (P <= 0 || ld < P)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0 and ld_pred >= n_support");
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  HostCall call;
+  int32_t rc = call.begin(model, pop, theta, P, batch, pop->hp.n_obs);
+  if (rc == PMX_OK) rc = call.run(model, pop, P, batch);
+  bool any_failed = false;
+  if (rc == PMX_OK) rc = call.finish(status, pred, ld, &any_failed);
+  if (rc != PMX_OK) return rc;
+  return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
+}
+
+// ll[s][p] (matrix shape) or ll[s] (batch shape: subject s with theta row s, likelihood/mod.rs:119-177)
+int32_t loglik_host(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em, const double* theta,
+                    int64_t P, int batch, double* ll, int64_t ld_ll, uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !cpop || !em || !theta || !ll) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!batch && (P <= 0 || ld_ll < P)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0 and ld_ll >= n_support");
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  HostCall call;
+  int32_t rc = call.begin(model, pop, theta, P, batch, pop->hp.n_subjects);
+  if (rc != PMX_OK) return rc;
+  HostWorkspace* ws = call.ws;
+  const int32_t* d_sigma_err = nullptr;
+  LLRequest req{em, call.d_out(), call.Pd, &d_sigma_err};
+  if ((rc = call.run(model, pop, P, batch, &req)) != PMX_OK) return rc;
+  if (d_sigma_err) {  // ErrorModelError::NegativeSigma / NonFiniteSigma (error_model.rs:1073-1077), found on the device
+    PMX_HIP(hipMemcpyAsync(ws->h_flag, d_sigma_err, sizeof(int32_t), hipMemcpyDeviceToHost, ws->compute));
+    PMX_HIP(hipStreamSynchronize(ws->compute));
+    const int32_t n_bad = *ws->h_flag;
+    if (n_bad > 0)
+      return fail(PMX_ERR_ERROR_MODEL, "NegativeSigma / NonFiniteSigma for " + std::to_string(n_bad) + " observation(s)");
+  }
+  bool any_failed = false;
+  if ((rc = call.finish(status, ll, ld_ll, &any_failed)) != PMX_OK) return rc;
+  if (!any_failed) return PMX_OK;
+  if (!batch) return fail(PMX_ERR_PAIR_FAILED, kPairFailed);
+  // log_likelihood_batch maps a failed subject to -inf instead of failing the call (likelihood/mod.rs:137-140):
+  // the status array names them, the caller's row is overwritten here
+  std::vector<uint8_t> hst(call.n_status);
+  PMX_HIP(hipMemcpy(hst.data(), ws->d_status, call.n_status, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < call.n_status; ++i)
+    if (hst[i] != PMX_PAIR_OK) ll[i] = -std::numeric_limits<double>::infinity();
+  return PMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t pmx_predict(const pmx_model* model, const pmx_population* pop, const double* theta, int64_t n_support,
+                    double* pred, int64_t ld_pred, uint8_t* status) {
+  return predict_host(model, pop, theta, n_support, 0, pred, ld_pred, status);
+}
+int32_t pmx_predict_batch(const pmx_model* model, const pmx_population* pop, const double* theta, double* pred,
+                          uint8_t* status) {
+  return predict_host(model, pop, theta, 1, 1, pred, 1, status);
+}
+int32_t pmx_loglik(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
+                   int64_t n_support, double* ll, int64_t ld_ll, uint8_t* status) {
+  return loglik_host(model, pop, em, theta, n_support, 0, ll, ld_ll, status);
+}
+int32_t pmx_loglik_batch(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
+                         double* ll, uint8_t* status) {
+  return loglik_host(model, pop, em, theta, 1, 1, ll, 1, status);
+}
+
+}  // extern "C"

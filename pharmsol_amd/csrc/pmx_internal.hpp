@@ -1,6 +1,8 @@
 // pmx_internal.hpp — what the translation units of the C ABI share: the opaque handles of include/pmx.h, the device
 // stream of a (population, model flavour) pair and the developer switches.
-//   pmx_api.cpp     C entry points, model creation and checks, host-pointer workspace, debug views
+//   pmx_api.cpp     error text, populations, device-pointer entry points, debug views, measurement helpers
+//   pmx_model.cpp   model creation: path table, descriptor checks, resolve, build; the hiprtc source views
+//   pmx_host.cpp    host-pointer entry points and the workspace they keep on the population
 //   pmx_stream.cpp  DeviceStream: plan (pmx_plan.cpp plan_stream), upload, log-likelihood slots
 //   pmx_launch.cpp  compile key, route decision, enqueue
 #pragma once
@@ -24,6 +26,7 @@ namespace pmx {
 // the calling thread's error text (pmx_last_error) and kernel name (pmx_last_kernel_name): pmx_api.cpp
 int32_t set_error(int32_t code, const std::string& msg);
 void set_kernel_name(const char* name);
+inline void clear_error() { (void)set_error(PMX_OK, std::string()); }  // the first act of every entry point
 
 // Developer switches (INTEGRATION.md "environment switches").  Read ONCE, at the first call that needs them: a
 // std::getenv per launch is measurable on the 11 us C2 pass.  pmx_debug_reload_env() re-reads them (tuning scripts
@@ -138,7 +141,7 @@ struct DeviceStream {
   }
 };
 
-struct HostWorkspace;  // pmx_api.cpp: what the host-pointer entry points keep between calls
+struct HostWorkspace;  // pmx_host.cpp: what the host-pointer entry points keep between calls
 
 struct pmx_population {
   int device = 0;
@@ -156,7 +159,7 @@ struct pmx_population {
   std::vector<void*> ll_allocs;
   std::vector<std::unique_ptr<DeviceStream>> streams;  // one per model flavour, built lazily
   pmx_population();
-  ~pmx_population();  // (pmx_api.cpp, where HostWorkspace is complete)
+  ~pmx_population();  // (pmx_host.cpp, where HostWorkspace is complete; pmx_population_destroy too)
 };
 
 struct pmx_model {

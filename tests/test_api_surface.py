@@ -5,7 +5,10 @@
 failure -> -inf rule (likelihood/mod.rs:119-177, residual_error.rs:178-271), the host-pointer entry points' persistent
 workspace (pinned or pageable outputs); what every model-creation path refuses of an ODE descriptor's solver fields."""
 import ctypes as C
+import importlib.util
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -196,6 +199,90 @@ def test_host_pointer_entry_points_reuse_their_workspace_and_take_pinned_or_page
     assert rc == _abi.PMX_ERR_PAIR_FAILED and np.isnan(sink[:, 3]).all() and np.isfinite(np.delete(sink, 3, axis=1)).all()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("want_status", [False, True])
+def test_host_pointer_forms_return_what_their_device_twins_return(want_status):
+    """pmx_predict, pmx_predict_batch, pmx_loglik and pmx_loglik_batch upload theta, run the kernels of their *_device
+    twins and copy out: the same bits, in a padded matrix (ld 8 for 5 support points, the padding left alone), with and
+    without a status array.  One pair with complex eigenvalues: PMX_ERR_PAIR_FAILED from the matrix forms and from
+    pmx_predict_batch, -inf in that row and PMX_OK from pmx_loglik_batch.  A negative-sigma error model is refused with
+    PMX_ERR_ERROR_MODEL, and the next call on the same population succeeds."""
+    import torch
+
+    L = _ffi.lib()
+    m, subs, thb, rem = _batch_case(43)
+    flat = m.flatten(Data(subs))
+    dm, pop = runtime._as_model(m), runtime.DevicePopulation(flat, 0)
+    S, NO, P, LD = pop.n_subjects, pop.n_observations, 5, 8
+    assert S == 43
+    th = synth.theta_c3(P)
+    th[3, 1], th[3, 0], th[3, 2] = -3.0, 1.0, 1.0    # support point 3: complex eigenvalues
+    thb[5, 1], thb[5, 0], thb[5, 2] = -3.0, 1.0, 1.0  # batch forms: subject 5
+    em = rem.to_c(m)
+    emp = C.cast(em, C.c_void_p)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def same_bits(a, b):
+        return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+    def status_arg(shape):
+        st = np.full(shape, 9, dtype=np.uint8) if want_status else None
+        return st, (st.ctypes.data if want_status else None)
+
+    # ---- the device twins
+    d_pred = torch.full((NO, LD), -7.0, dtype=torch.float64, device=dev)
+    _, d_st = runtime.predict(m, pop, th, pred=d_pred[:, :P])
+    d_predb, d_stb = runtime.predict(m, pop, thb, batch=True)
+    d_ll = torch.full((S, LD), -7.0, dtype=torch.float64, device=dev)
+    _, d_llst = runtime.loglik(m, pop, rem, th, ll=d_ll[:, :P])
+    d_llb = torch.empty((S,), dtype=torch.float64, device=dev)
+    d_llbst = torch.zeros((S,), dtype=torch.uint8, device=dev)
+    t_thb = torch.as_tensor(thb, device=dev)
+    _ffi.check(L.pmx_loglik_batch_device(dm.handle, pop.handle, emp, t_thb.data_ptr(), d_llb.data_ptr(), d_llbst.data_ptr(), stream))
+    torch.cuda.synchronize()
+    d_pred, d_st, d_predb, d_stb = d_pred.cpu().numpy(), d_st.cpu().numpy(), d_predb.cpu().numpy(), d_stb.cpu().numpy()
+    d_ll, d_llst, d_llb, d_llbst = d_ll.cpu().numpy(), d_llst.cpu().numpy(), d_llb.cpu().numpy(), d_llbst.cpu().numpy()
+    assert d_st[:, 3].all() and not np.delete(d_st, 3, axis=1).any() and d_stb[5] and d_llbst[5] and d_llbst.sum() == d_llbst[5]
+    assert (d_pred[:, P:] == -7.0).all() and (d_ll[:, P:] == -7.0).all()
+
+    # ---- pmx_predict
+    out = np.full((NO, LD), -7.0)
+    st, stp = status_arg((S, P))
+    rc = L.pmx_predict(dm.handle, pop.handle, th.ctypes.data, P, out.ctypes.data, LD, stp)
+    assert rc == _abi.PMX_ERR_PAIR_FAILED and same_bits(out, d_pred)
+    assert st is None or np.array_equal(st, d_st)
+    # ---- pmx_predict_batch
+    outb = np.full((NO,), -7.0)
+    st, stp = status_arg((S,))
+    rc = L.pmx_predict_batch(dm.handle, pop.handle, thb.ctypes.data, outb.ctypes.data, stp)
+    assert rc == _abi.PMX_ERR_PAIR_FAILED and same_bits(outb, d_predb)
+    assert st is None or np.array_equal(st, d_stb)
+    # ---- pmx_loglik
+    ll = np.full((S, LD), -7.0)
+    st, stp = status_arg((S, P))
+    rc = L.pmx_loglik(dm.handle, pop.handle, emp, th.ctypes.data, P, ll.ctypes.data, LD, stp)
+    assert rc == _abi.PMX_ERR_PAIR_FAILED and same_bits(ll, d_ll)
+    assert st is None or np.array_equal(st, d_llst)
+    # ---- pmx_loglik_batch: the failed subject becomes -inf, the call succeeds
+    llb = np.full((S,), -7.0)
+    st, stp = status_arg((S,))
+    rc = L.pmx_loglik_batch(dm.handle, pop.handle, emp, thb.ctypes.data, llb.ctypes.data, stp)
+    assert rc == _abi.PMX_OK and llb[5] == -np.inf and same_bits(np.delete(llb, 5), np.delete(d_llb, 5))
+    assert st is None or np.array_equal(st, d_llbst)
+    # ---- an error return leaves the workspace usable
+    bad = (AssayErrorModels.empty().add(0, AssayErrorModel.proportional(ErrorPoly(0.02, 0.15, 0.0, 0.0), -1.0))
+           .add(1, AssayErrorModel.additive(ErrorPoly(0.1, 0.1, 0.0, 0.0), 0.0))).to_c(m)
+    ll2 = np.full((S, LD), -7.0)
+    st, stp = status_arg((S, P))
+    rc = L.pmx_loglik(dm.handle, pop.handle, C.cast(bad, C.c_void_p), th.ctypes.data, P, ll2.ctypes.data, LD, stp)
+    assert rc == _abi.PMX_ERR_ERROR_MODEL and "NegativeSigma" in L.pmx_last_error().decode()
+    ll2[:] = -7.0
+    rc = L.pmx_loglik(dm.handle, pop.handle, emp, th.ctypes.data, P, ll2.ctypes.data, LD, stp)
+    assert rc == _abi.PMX_ERR_PAIR_FAILED and same_bits(ll2, d_ll)
+    assert st is None or np.array_equal(st, d_llst)
+
+
 # --------------------------------------------------------------------------- ODE solver fields (no GPU, no compiler)
 _SIG = "double t, const double* x, const double* p, const double* cov, const double* rateiv, const double* derived, double* "
 _ORAL_SRC = (f"PMX_DEVICE void pmx_dynamics({_SIG}dx) {{ dx[0] = -p[0] * x[0]; dx[1] = p[0] * x[0] - p[1] * x[1] + rateiv[0]; }}\n"
@@ -236,3 +323,80 @@ def test_every_creation_path_refuses_unknown_solvers_and_missing_tolerances():
         for solver in need_tol:
             refused(path, ode_solver=solver, ode_rtol=0.0)
             refused(path, ode_solver=solver, ode_atol=0.0)
+
+
+# --------------------------------------------------------------------------- model creation (no GPU; hiprtc needs none)
+_HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _load_refusals():
+    spec = importlib.util.spec_from_file_location("gen_model_refusals", os.path.join(_HERE, "golden", "gen_model_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(_HERE, "golden", "model_refusals.json")) as f:
+        return gen, json.load(f)
+
+
+# One check that carried two wordings keeps the more specific one on every path: recorded text -> {fault: text now}
+_REWORDED = {
+    "bind entry out of range": {"bind_index": "bind index out of range", "bind_index_negative": "bind index out of range",
+                                "bind_derived_index": "bind derived index out of range",
+                                "bind_src": "bind.src must be PRIMARY or DERIVED"},
+}
+
+
+def test_every_creation_path_answers_as_recorded_before_the_path_table():
+    """tests/golden/model_refusals.json holds what the five creation paths answered - return code, error text, and the
+    SHA-256 of every translation unit the debug calls returned - before the four validators became one path table
+    (tests/golden/gen_model_refusals.py; one fault per case, both sides of every bound the paths differ in).  Every case
+    is replayed: same code, same text but for the rewordings of _REWORDED, a handle or text exactly when the code is 0,
+    the same translation unit."""
+    gen, fx = _load_refusals()
+    L = _ffi.lib()
+    assert len(fx["cases"]) > 200 and sum("sha256" in c for c in fx["cases"]) >= 20
+    for c in fx["cases"]:
+        rc, text, null, sha = gen.run_case(L, fx, c)
+        want = _REWORDED.get(c["text"], {}).get(c["name"].split("/")[-1], c["text"])
+        assert (rc, text) == (c["code"], want), c["name"]
+        assert null == (rc != _abi.PMX_OK), c["name"]
+        assert sha == c.get("sha256"), c["name"]
+    reworded = [c["name"] for c in fx["cases"] if c["text"] in _REWORDED]
+    assert len(reworded) == 8  # four faults of bind[] on the two paths that said "bind entry out of range"
+
+
+def test_the_debug_calls_show_what_creation_compiles():
+    """A custom diffeq body with five lagged inputs is created on the general ODE walker (the state-machine kernels keep
+    four lag cursors): pmx_debug_jit_source shows that translation unit - pmx_ode_user.hpp - and the same text as
+    pmx_debug_jit_source_user for the closure set creation passes on.  What creation refuses, the debug calls refuse:
+    the general walker's row (init_param here) and an unknown eq_kind."""
+    gen, fx = _load_refusals()
+    L = _ffi.lib()
+    five = [[f"lag_param[{i}]", 2] for i in range(5)] + [["ndrugs", 5]]
+
+    def text_of(call, edits, **how):
+        case = dict(base="custom", edits=edits, call=call, source="body_init", **how)
+        d = gen.make_desc(fx["bases"]["custom"], edits)
+        h = C.c_void_p()
+        if call == "debug_jit_source":
+            rc = L.pmx_debug_jit_source(C.byref(d), fx["sources"][case["source"]].encode(), how["has_init"], C.byref(h))
+        else:
+            rc = L.pmx_debug_jit_source_user(C.byref(d), fx["sources"][case["source"]].encode(), how["fns"], C.byref(h))
+        if rc != _abi.PMX_OK:
+            assert not h.value
+            return rc, L.pmx_last_error().decode()
+        try:
+            return rc, C.string_at(h.value).decode()
+        finally:
+            L.pmx_free_text(h)
+
+    body = _abi.PMX_FN_DYNAMICS | _abi.PMX_FN_OUTPUTS
+    for has_init in (0, 1):
+        rc, tu = text_of("debug_jit_source", five, has_init=has_init)
+        assert rc == _abi.PMX_OK and '#include "pmx_ode_user.hpp"' in tu and '#include "pmx_ode.hpp"' not in tu
+        assert (rc, tu) == text_of("debug_jit_source_user", five, fns=body | (_abi.PMX_FN_INIT if has_init else 0))
+        rc4, tu4 = text_of("debug_jit_source", five[1:], has_init=has_init)  # four lagged inputs: the state-machine kernels
+        assert rc4 == _abi.PMX_OK and '#include "pmx_ode.hpp"' in tu4
+    for call, how in (("debug_jit_source", dict(has_init=0)), ("debug_jit_source_user", dict(fns=body))):
+        assert text_of(call, five + [["init_param[0]", 3]], **how) == (_abi.PMX_ERR_INVALID_ARGUMENT, "init_param out of range")
+        assert text_of(call, five[1:] + [["init_param[0]", 3]], **how)[0] == _abi.PMX_OK  # (the custom path does not read init_param)
+    assert text_of("debug_jit_source_user", [["eq_kind", 7]], fns=_abi.PMX_FN_ROUTE_LAG) == (_abi.PMX_ERR_INVALID_ARGUMENT, "unknown eq_kind")
