@@ -1,14 +1,8 @@
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE 1
 #endif
-// pmx_jit.cpp — run-time compilation of user ODE models (hiprtc -> gfx950 code object -> hipModule).
-//
-// The reference lets a user write `diffeq` / `out` / `init` as closures (ode/mod.rs:115-132) or in its DSL, which
-// it JIT-compiles with cranelift for the CPU (src/dsl/jit.rs).  Here the user's bodies are C/HIP device functions
-// with the reference's compiled-kernel argument order (src/dsl/native.rs:45-53:
-// t, states, params, covariates, routes, derived, out); they are wrapped in a model policy and instantiated into
-// the SAME walkers the built-in diffeq bodies use (pmx_ode.hpp), so event handling, lag/fa, RK4 stepping and the
-// fused log-likelihood are shared code, not a second implementation.
+// pmx_jit.cpp — run-time compilation of user models (hiprtc -> gfx950 code object -> hipModule).  The text that is
+// compiled is pmx_jit_source.cpp's.
 #include "pmx_jit.hpp"
 #include "pmx_devtypes.hpp"
 #include "pmx_jit_cache.hpp"
@@ -20,7 +14,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <sstream>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -28,372 +21,6 @@
 #include "pmx_jit_headers.inc"
 
 namespace pmx {
-
-namespace {
-
-const char* const kSolv[SOLV_AUTO + 1] = {"pmx::SOLV_RK4", "pmx::SOLV_ADAPT", "pmx::SOLV_CHECKED", "pmx::SOLV_AUTO"};  // (as the wrappers spell them)
-
-// Policy of a user ANALYTICAL model: every closure of Analytical::new(eq, seq_eq, lag, fa, init, out)
-// (analytical/mod.rs:102-118) as a static device function.  A closure the user's source defines is forwarded to
-// (argument order of the reference's compiled kernels, src/dsl/native.rs:45-53); one it leaves out is generated here from
-// the descriptor's closed form (lag_param / fa_param / init_param / out[] / bind[]), so the walker sees one shape.
-std::string analytical_translation_unit(const JitSpec& s) {
-  const pmx_model_desc& d = s.desc;
-  const uint32_t f = s.fns;
-  const bool user_eq = d.kernel == PMX_K_CUSTOM;
-  const int nin = d.ndrugs > 0 ? d.ndrugs : 1;
-  bool desc_lag = false, desc_fa = false, bind_derived = false;
-  for (int i = 0; i < PMX_MAX_INPUTS; ++i) {
-    desc_lag |= d.lag_param[i] >= 0;
-    desc_fa |= d.fa_param[i] >= 0;
-  }
-  for (int j = 0; j < d.n_bind; ++j) bind_derived |= d.bind[j].src == PMX_SRC_DERIVED;
-  const bool has_lag = (f & PMX_FN_ROUTE_LAG) || desc_lag;
-  const bool has_fa = (f & PMX_FN_ROUTE_BIOAVAILABILITY) || desc_fa;
-  const bool has_seq = (f & PMX_FN_SEQ_EQ) != 0;
-  const bool has_derive = (f & PMX_FN_DERIVE) != 0;
-  const bool static_coef = !user_eq && !has_seq && !bind_derived;
-  std::ostringstream o;
-  o << "// generated by libpmx_hip (pmx_jit.cpp)\n"
-       "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
-       "typedef int int32_t; typedef unsigned int uint32_t; typedef long long int64_t; typedef unsigned long long uint64_t;\n"
-       "#define PMX_DEVICE __device__ __forceinline__\n"
-    << (s.big_lists ? "#define PMX_USER_BIG_LISTS 1\n" : "") << "#define PMX_USER_LAG_KEPT " << pmx::kUserLagKept << "\n"
-    << "#include \"pmx_analytical.hpp\"\n"
-       "// ---------------------------------------------------------------- user source\n"
-       "#line 1 \"model\"\n"
-    << s.source
-    << "\n// ---------------------------------------------------------------- policy + entry points\n"
-       "namespace pmx { namespace {\n"
-       "struct UserModel {\n"
-    << "  static constexpr int NS = " << d.nstates << ", NP = " << d.nparams << ", NIN = " << nin << ", NOUT = " << d.nout
-    << ", NCOV = " << d.n_covariates << ", NDER = " << d.n_derived << ";\n"
-    << "  static constexpr int KID = " << (user_eq ? -1 : d.kernel) << ", PM = " << ((d.pmetrics_indexing && !user_eq) ? 1 : 0)
-    << ", RATE_INPUT = " << ((d.pmetrics_indexing && !user_eq) ? 1 : 0) << ";\n"
-    << "  static constexpr bool COV_ABS = " << (d.cov_time_mode == PMX_COV_TIME_SEGMENT_END_ABS ? "true" : "false")
-    << ", HAS_LAG = " << (has_lag ? "true" : "false") << ", HAS_FA = " << (has_fa ? "true" : "false")
-    << ", HAS_SEQ = " << (has_seq ? "true" : "false") << ", HAS_DERIVE = " << (has_derive ? "true" : "false")
-    << ", STATIC_COEF = " << (static_coef ? "true" : "false") << ";\n";
-  // derive
-  o << "  static __device__ __forceinline__ void derive(double t, const double* p, const double* cov, double* der) {\n";
-  if (has_derive) o << "    pmx_derive(t, nullptr, p, cov, nullptr, nullptr, der);\n";
-  o << "  }\n";
-  // lag
-  o << "  static __device__ __forceinline__ void lag(double t, const double* p, const double* cov, const double* der, double* lag) {\n";
-  if (f & PMX_FN_ROUTE_LAG) {
-    o << "    pmx_route_lag(t, nullptr, p, cov, nullptr, der, lag);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_INPUTS && i < nin; ++i)
-      if (d.lag_param[i] >= 0) o << "    lag[" << i << "] = p[" << d.lag_param[i] << "];\n";
-  }
-  o << "  }\n";
-  // fa
-  o << "  static __device__ __forceinline__ void fa(double t, const double* p, const double* cov, const double* der, double* fa) {\n";
-  if (f & PMX_FN_ROUTE_BIOAVAILABILITY) {
-    o << "    pmx_route_bioavailability(t, nullptr, p, cov, nullptr, der, fa);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_INPUTS && i < nin; ++i)
-      if (d.fa_param[i] >= 0) o << "    fa[" << i << "] = p[" << d.fa_param[i] << "];\n";
-  }
-  o << "  }\n";
-  // init
-  o << "  static __device__ __forceinline__ void init(const double* p, const double* cov, const double* der, double (&x)[NS]) {\n";
-  if (f & PMX_FN_INIT) {
-    o << "    pmx_init(0.0, x, p, cov, nullptr, der, x);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_STATES && i < d.nstates; ++i)
-      if (d.init_param[i] >= 0) o << "    x[" << i << "] = p[" << d.init_param[i] << "];\n";
-  }
-  o << "  }\n";
-  // out
-  o << "  static __device__ __forceinline__ void out(double t, const double (&x)[NS], const double* p, const double* cov,\n"
-       "                                             const double* der, double (&y)[NOUT]) {\n";
-  if (f & PMX_FN_OUTPUTS) {
-    o << "    pmx_outputs(t, x, p, cov, nullptr, der, y);\n";
-  } else {
-    for (int q = 0; q < d.nout && q < PMX_MAX_OUT; ++q) {
-      o << "    y[" << q << "] = x[" << d.out[q].state << "]";
-      if (d.out[q].vol_src == PMX_SRC_PRIMARY) o << " / p[" << d.out[q].vol_index << "]";
-      if (d.out[q].vol_src == PMX_SRC_DERIVED) o << " / der[" << d.out[q].vol_index << "]";
-      o << ";\n";
-    }
-  }
-  o << "  }\n";
-  // seq_eq: `out` = the working parameter vector, modified in place; p = the support point as given
-  o << "  static __device__ __forceinline__ void seq(double t, const double* p, const double* cov, double* pw) {\n";
-  if (has_seq) o << "    pmx_seq_eq(t, nullptr, p, cov, nullptr, nullptr, pw);\n";
-  o << "  }\n";
-  // eq
-  o << "  static __device__ __forceinline__ void eq(double dt, const double (&x)[NS], const double* pw, const double* cov,\n"
-       "                                            const double* rate, const double* der, double (&xn)[NS]) {\n";
-  if (user_eq) o << "    pmx_eq(dt, x, pw, cov, rate, der, xn);\n";
-  o << "  }\n";
-  // kernel-order parameters of a built-in structure (the macro's projection, expand/analytical.rs:208-294)
-  o << "  static __device__ __forceinline__ void kernel_params(const double* pw, const double* der, double* kp) {\n";
-  if (!user_eq) {
-    const int np = d.n_bind;
-    if (np == 0) {
-      o << "    for (int j = 0; j < kernel_nparams(KID); ++j) kp[j] = pw[j];\n";
-    } else {
-      for (int j = 0; j < np; ++j)
-        o << "    kp[" << j << "] = " << (d.bind[j].src == PMX_SRC_DERIVED ? "der[" : "pw[") << d.bind[j].index << "];\n";
-    }
-  }
-  o << "  }\n};\n}}  // namespace\n";
-  for (int ll = 0; ll < 2; ++ll) {
-    o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_agrid_" << ll
-      << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t s_chunk,\n"
-         "    int32_t n_ptiles, double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-         "  pmx::user_grid_body<pmx::UserModel, "
-      << (ll ? "true" : "false") << ">(m, ops, theta, P, S, s_chunk, n_ptiles, pred, ld, status);\n}\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_apair_" << ll
-      << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t batch,\n"
-         "    double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-         "  pmx::user_pair_body<pmx::UserModel, "
-      << (ll ? "true" : "false") << ">(m, ops, theta, P, S, batch, pred, ld, status);\n}\n";
-  }
-  return o.str();
-}
-
-// Policy of a user ODE model whose lag / fa / derive are closures too, or whose dynamics takes the bolus vector
-// (ODE::new(diffeq, lag, fa, init, out), ode/mod.rs:115-132): the custom-body policy of pmx_ode.hpp with `derive` folded
-// into every closure (the way every macro-lowered closure starts) plus lag / fa / the bolus form of the dynamics for
-// pmx_ode_user.hpp.  Closures the source leaves out come from the descriptor (lag_param / fa_param / init_param).
-std::string ode_user_translation_unit(const JitSpec& s) {
-  const pmx_model_desc& d = s.desc;
-  const uint32_t f = s.fns;
-  const int nin = d.ndrugs > 0 ? d.ndrugs : 1;
-  bool desc_lag = false, desc_fa = false, desc_init = false;
-  for (int i = 0; i < PMX_MAX_INPUTS; ++i) {
-    desc_lag |= d.lag_param[i] >= 0;
-    desc_fa |= d.fa_param[i] >= 0;
-  }
-  for (int i = 0; i < PMX_MAX_STATES && i < d.nstates; ++i) desc_init |= d.init_param[i] >= 0;
-  const bool has_lag = (f & PMX_FN_ROUTE_LAG) || desc_lag;
-  const bool has_fa = (f & PMX_FN_ROUTE_BIOAVAILABILITY) || desc_fa;
-  const bool has_derive = (f & PMX_FN_DERIVE) != 0;
-  const bool has_init = (f & PMX_FN_INIT) || desc_init;
-  const bool bolus_arg = (f & PMX_FN_DYNAMICS_BOLUS) != 0;
-  const int nder = d.n_derived > 0 ? d.n_derived : 1;
-  auto B = [](bool b) { return b ? "true" : "false"; };
-  // `double der[..]` + the derive call at time expression `t`, or a null pointer
-  const std::string der_decl = has_derive ? "    double der[" + std::to_string(nder) + "];\n    for (int i = 0; i < " + std::to_string(nder) +
-                                                "; ++i) der[i] = 0.0;\n    pmx_derive(t, nullptr, p, cov, nullptr, nullptr, der);\n"
-                                          : "    const double* der = nullptr;\n";
-  std::ostringstream o;
-  o << "// generated by libpmx_hip (pmx_jit.cpp)\n"
-       "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
-       "typedef int int32_t; typedef unsigned int uint32_t; typedef long long int64_t; typedef unsigned long long uint64_t;\n"
-       "#define PMX_DEVICE __device__ __forceinline__\n"
-    << (s.big_lists ? "#define PMX_USER_BIG_LISTS 1\n" : "") << "#define PMX_USER_LAG_KEPT " << pmx::kUserLagKept << "\n"
-    << "#include \"pmx_ode_user.hpp\"\n"
-       "// ---------------------------------------------------------------- user source\n"
-       "#line 1 \"model\"\n"
-    << s.source
-    << "\n// ---------------------------------------------------------------- policy + entry points\n"
-       "namespace pmx { namespace {\n"
-       "struct UserModel {\n"
-       "  static constexpr bool CUSTOM = true;\n"
-    << "  static constexpr int NS = " << d.nstates << ", NP = " << d.nparams << ", CENTRAL = 0, NR = " << nin << ", NIN = " << nin
-    << ", NOUT = " << d.nout << ", NCOV = " << d.n_covariates << ", NDER = " << d.n_derived << ";\n"
-    << "  static constexpr bool HAS_INIT = " << B(has_init) << ", HAS_DERIVE = " << B(has_derive) << ", HAS_LAG = " << B(has_lag)
-    << ", HAS_FA = " << B(has_fa) << ", BOLUS_ARG = " << B(bolus_arg) << ";\n";
-  o << "  static __device__ __forceinline__ void derive(double t, const double* p, const double* cov, double* der) {\n";
-  if (has_derive) o << "    pmx_derive(t, nullptr, p, cov, nullptr, nullptr, der);\n";
-  o << "  }\n";
-  o << "  static __device__ __forceinline__ void lag(double t, const double* p, const double* cov, const double* der, double* lag) {\n";
-  if (f & PMX_FN_ROUTE_LAG) {
-    o << "    pmx_route_lag(t, nullptr, p, cov, nullptr, der, lag);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_INPUTS && i < nin; ++i)
-      if (d.lag_param[i] >= 0) o << "    lag[" << i << "] = p[" << d.lag_param[i] << "];\n";
-  }
-  o << "  }\n";
-  o << "  static __device__ __forceinline__ void fa(double t, const double* p, const double* cov, const double* der, double* fa) {\n";
-  if (f & PMX_FN_ROUTE_BIOAVAILABILITY) {
-    o << "    pmx_route_bioavailability(t, nullptr, p, cov, nullptr, der, fa);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_INPUTS && i < nin; ++i)
-      if (d.fa_param[i] >= 0) o << "    fa[" << i << "] = p[" << d.fa_param[i] << "];\n";
-  }
-  o << "  }\n";
-  // dynamics during integration: bolus = 0
-  o << "  static __device__ __forceinline__ void rhs(double t, const double* p, const double (&x)[NS], const double (&r)[NR],\n"
-       "                                             const double* cov, double (&dx)[NS]) {\n"
-       "    for (int i = 0; i < NS; ++i) dx[i] = 0.0;\n"
-    << der_decl;
-  if (bolus_arg)
-    o << "    double zb[NIN];\n    for (int i = 0; i < NIN; ++i) zb[i] = 0.0;\n"
-         "    pmx_dynamics_bolus(t, x, p, cov, r, zb, der, dx);\n";
-  else
-    o << "    pmx_dynamics(t, x, p, cov, r, der, dx);\n";
-  o << "  }\n";
-  // the DiffEq as the reference calls it for a bolus event
-  o << "  static __device__ __forceinline__ void rhs_bolus(double t, const double* p, const double (&x)[NS], const double (&r)[NR],\n"
-       "                                                   const double (&b)[NIN], const double* cov, double (&dx)[NS]) {\n"
-       "    for (int i = 0; i < NS; ++i) dx[i] = 0.0;\n";
-  if (bolus_arg) o << der_decl << "    pmx_dynamics_bolus(t, x, p, cov, r, b, der, dx);\n";
-  o << "  }\n";
-  o << "  static __device__ __forceinline__ void out(double t, const double* p, const double (&x)[NS], const double* cov,\n"
-       "                                             double (&y)[NOUT]) {\n"
-    << der_decl << "    pmx_outputs(t, x, p, cov, nullptr, der, y);\n  }\n";
-  o << "  static __device__ __forceinline__ void init(const double* p, const double* cov, double (&x)[NS]) {\n";
-  if (f & PMX_FN_INIT) {
-    o << "    const double t = 0.0;\n" << der_decl << "    pmx_init(0.0, x, p, cov, nullptr, der, x);\n";
-  } else {
-    for (int i = 0; i < PMX_MAX_STATES && i < d.nstates; ++i)
-      if (d.init_param[i] >= 0) o << "    x[" << i << "] = p[" << d.init_param[i] << "];\n";
-  }
-  o << "  }\n};\n}}  // namespace\n";
-  static const char* kB[2] = {"false", "true"};
-  const SolvRange sv = jit_solv_range(s.solver);
-  for (int ll = 0; ll < 2; ++ll)
-    for (int ad = sv.begin; ad < sv.end; ++ad) {
-      o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_ugrid_" << ll << ad
-        << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t s_chunk,\n"
-           "    int32_t n_ptiles, double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-           "  pmx::uode_grid_body<pmx::UserModel, "
-        << kB[ll] << ", " << kSolv[ad] << ">(m, ops, theta, P, S, s_chunk, n_ptiles, pred, ld, status);\n}\n";
-      o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_upair_" << ll << ad
-        << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t batch,\n"
-           "    double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-           "  pmx::uode_pair_body<pmx::UserModel, "
-        << kB[ll] << ", " << kSolv[ad] << ">(m, ops, theta, P, S, batch, pred, ld, status);\n}\n";
-    }
-  return o.str();
-}
-
-}  // namespace
-
-// A built-in `diffeq` body whose parameters are DERIVED from covariates (the `derive`-style lines of an ode! model are
-// evaluated inside the body, with the covariates bound at the stage time t: pharmsol-macros/src/expand/ode.rs:126-185):
-// written out as the user-body source the hiprtc path compiles, so covariate lookup at every stage, lag / fa, both
-// solvers and the fused log-likelihood are the shared walkers' (pmx_ode.hpp).
-std::string ode_descriptor_source(const pmx_model_desc& d) {
-  static const char* const kRhs[PMX_ODE_MODEL_COUNT] = {
-      "  dx[0] = -kp[0] * x[0];\n",
-      "  dx[0] = -kp[0] * x[0];\n  dx[1] = kp[0] * x[0] - kp[1] * x[1];\n",
-      "  dx[0] = -kp[0] * x[0] - kp[1] * x[0] + kp[2] * x[1];\n  dx[1] = kp[1] * x[0] - kp[2] * x[1];\n",
-      "  dx[0] = -kp[1] * x[0];\n  dx[1] = -kp[0] * x[1] + kp[1] * x[0] - kp[2] * x[1] + kp[3] * x[2];\n"
-      "  dx[2] = kp[2] * x[1] - kp[3] * x[2];\n",
-      "  dx[0] = -(kp[0] + kp[1] + kp[2]) * x[0] + kp[3] * x[1] + kp[4] * x[2];\n  dx[1] = kp[1] * x[0] - kp[3] * x[1];\n"
-      "  dx[2] = kp[2] * x[0] - kp[4] * x[2];\n",
-      "  dx[0] = -kp[0] * x[0];\n  dx[1] = kp[0] * x[0] - (kp[1] + kp[2] + kp[3]) * x[1] + kp[4] * x[2] + kp[5] * x[3];\n"
-      "  dx[2] = kp[2] * x[1] - kp[4] * x[2];\n  dx[3] = kp[3] * x[1] - kp[5] * x[3];\n",
-      "  { const double cc = x[0] / kp[2]; dx[0] = -kp[0] * cc / (kp[1] + cc); }\n"};
-  static const int kCentral[PMX_ODE_MODEL_COUNT] = {0, 1, 0, 1, 0, 1, 0};
-  static const int kNP[PMX_ODE_MODEL_COUNT] = {1, 2, 3, 4, 5, 6, 3};
-  const char* const sig = "(double t, const double* x, const double* p, const double* cov, const double* rateiv, const double* derived, double* ";
-  std::ostringstream o;
-  o.precision(17);
-  // derived[i] = ((theta[src] * f0) * f1), factors from the covariates at t (the oracle's eval_derived)
-  o << "PMX_DEVICE void pmx_desc_derived(const double* p, const double* cov, double* d) {\n";
-  for (int i = 0; i < d.n_derived; ++i) {
-    o << "  d[" << i << "] = p[" << d.derived[i].src_param << "]";
-    for (int k = 0; k < d.derived[i].n_factors && k < PMX_MAX_FACTORS; ++k) {
-      const pmx_factor& f = d.derived[i].f[k];
-      if (f.op == PMX_F_POW) o << " * pow(cov[" << f.cov << "] / " << std::scientific << f.ref << ", " << f.coef << ")";
-      if (f.op == PMX_F_LIN) o << " * (1.0 + " << std::scientific << f.coef << " * (cov[" << f.cov << "] - " << f.ref << "))";
-    }
-    o << ";\n";
-  }
-  o << "}\n";
-  const int np = kNP[d.kernel];
-  o << "PMX_DEVICE void pmx_dynamics" << sig << "dx) {\n  double d[" << (d.n_derived > 0 ? d.n_derived : 1) << "];\n  d[0] = 0.0;\n"
-    << "  pmx_desc_derived(p, cov, d);\n  double kp[" << np << "];\n";
-  for (int j = 0; j < np; ++j) {
-    if (d.n_bind > 0)
-      o << "  kp[" << j << "] = " << (d.bind[j].src == PMX_SRC_DERIVED ? "d[" : "p[") << d.bind[j].index << "];\n";
-    else
-      o << "  kp[" << j << "] = p[" << j << "];\n";
-  }
-  o << kRhs[d.kernel];
-  for (int i = 0; i < d.ndrugs && i < PMX_MAX_INPUTS; ++i)  // dx[dest] += rateiv[i]  (expand/ode.rs:380-406)
-    o << "  dx[" << (d.infusion_dest[i] >= 0 ? d.infusion_dest[i] : kCentral[d.kernel]) << "] += rateiv[" << i << "];\n";
-  o << "}\n";
-  o << "PMX_DEVICE void pmx_outputs" << sig << "y) {\n  double d[" << (d.n_derived > 0 ? d.n_derived : 1) << "];\n  d[0] = 0.0;\n"
-    << "  pmx_desc_derived(p, cov, d);\n";
-  for (int q = 0; q < d.nout && q < PMX_MAX_OUT; ++q) {
-    o << "  y[" << q << "] = x[" << d.out[q].state << "]";
-    if (d.out[q].vol_src == PMX_SRC_PRIMARY) o << " / p[" << d.out[q].vol_index << "]";
-    if (d.out[q].vol_src == PMX_SRC_DERIVED) o << " / d[" << d.out[q].vol_index << "]";
-    o << ";\n";
-  }
-  o << "}\n";
-  o << "PMX_DEVICE void pmx_init" << sig << "xi) {\n";
-  for (int i = 0; i < d.nstates && i < PMX_MAX_STATES; ++i)
-    if (d.init_param[i] >= 0) o << "  xi[" << i << "] = p[" << d.init_param[i] << "];\n";
-  o << "}\n";
-  return o.str();
-}
-
-std::string analytical_descriptor_source(const pmx_model_desc& d) {
-  std::ostringstream o;
-  o.precision(17);
-  o << "PMX_DEVICE void pmx_derive(double t, const double* x, const double* p, const double* cov, const double* rateiv, "
-       "const double* derived, double* d) {\n";
-  for (int i = 0; i < d.n_derived; ++i) {  // derived[i] = ((theta[src] * f0) * f1): the oracle's eval_derived, the kernels' apply_factors
-    o << "  d[" << i << "] = p[" << d.derived[i].src_param << "]";
-    for (int k = 0; k < d.derived[i].n_factors && k < PMX_MAX_FACTORS; ++k) {
-      const pmx_factor& f = d.derived[i].f[k];
-      if (f.op == PMX_F_POW) o << " * pow(cov[" << f.cov << "] / " << std::scientific << f.ref << ", " << f.coef << ")";
-      if (f.op == PMX_F_LIN) o << " * (1.0 + " << std::scientific << f.coef << " * (cov[" << f.cov << "] - " << f.ref << "))";
-    }
-    o << ";\n";
-  }
-  o << "}\n";
-  return o.str();
-}
-
-std::string jit_translation_unit(const JitSpec& s) {
-  if (s.analytical) return analytical_translation_unit(s);
-  if (s.ode_user) return ode_user_translation_unit(s);
-  std::ostringstream o;
-  o << "// generated by libpmx_hip (pmx_jit.cpp)\n"
-       "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
-       "typedef int int32_t; typedef unsigned int uint32_t; typedef long long int64_t; typedef unsigned long long uint64_t;\n"
-       "#define PMX_DEVICE __device__ __forceinline__\n"
-       "#include \"pmx_ode.hpp\"\n"
-       "// ---------------------------------------------------------------- user source\n"
-       "#line 1 \"model\"\n"
-    << s.source
-    << "\n// ---------------------------------------------------------------- policy + entry points\n"
-       "namespace pmx { namespace {\n"
-       "struct UserModel {\n"
-       "  static constexpr bool CUSTOM = true;\n"
-    << "  static constexpr int NS = " << s.nstates << ", NP = " << s.nparams << ", CENTRAL = 0, NR = "
-    << (s.ninputs > 0 ? s.ninputs : 1) << ", NOUT = " << s.nout << ", NCOV = " << s.ncov << ";\n"
-    << "  static constexpr bool HAS_INIT = " << (s.has_init ? "true" : "false") << ";\n"
-    << "  static __device__ __forceinline__ void rhs(double t, const double* p, const double (&x)[NS], const double (&r)[NR],\n"
-       "                                             const double* cov, double (&dx)[NS]) {\n"
-       "    for (int i = 0; i < NS; ++i) dx[i] = 0.0;\n"
-       "    pmx_dynamics(t, x, p, cov, r, nullptr, dx);\n"
-       "  }\n"
-       "  static __device__ __forceinline__ void out(double t, const double* p, const double (&x)[NS], const double* cov,\n"
-       "                                             double (&y)[NOUT]) {\n"
-       "    pmx_outputs(t, x, p, cov, nullptr, nullptr, y);\n"
-       "  }\n"
-       "  static __device__ __forceinline__ void init(const double* p, const double* cov, double (&x)[NS]) {\n";
-  if (s.has_init) o << "    pmx_init(0.0, x, p, cov, nullptr, nullptr, x);\n";
-  o << "  }\n};\n}}  // namespace\n";
-  static const char* kLag[2] = {"false", "true"};
-  const SolvRange sv = jit_solv_range(s.solver);
-  for (int lag = 0; lag < 2; ++lag)
-    for (int ll = 0; ll < 2; ++ll)
-     for (int ad = sv.begin; ad < sv.end; ++ad) {
-      o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_grid_" << lag << ll << ad
-        << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t s_chunk,\n"
-           "    int32_t n_ptiles, double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-           "  pmx::ode_grid_body<pmx::UserModel, "
-        << kLag[lag] << ", " << kLag[ll] << ", " << kSolv[ad] << ">(m, ops, theta, P, S, s_chunk, n_ptiles, pred, ld, status);\n}\n";
-      o << "extern \"C\" __global__ __launch_bounds__(256) void pmx_jit_pair_" << lag << ll << ad
-        << "(pmx::DevModel m, pmx::DevOps ops, const double* __restrict__ theta, int64_t P, int64_t S, int32_t batch,\n"
-           "    double* __restrict__ pred, int64_t ld, uint8_t* __restrict__ status) {\n"
-           "  pmx::ode_pair_body<pmx::UserModel, "
-        << kLag[lag] << ", " << kLag[ll] << ", " << kSolv[ad] << ">(m, ops, theta, P, S, batch, pred, ld, status);\n}\n";
-    }
-  return o.str();
-}
 
 // The hiprtc entry points: the copy the process linked (inside a PyTorch process: PyTorch's), or - PMX_HIPRTC_LIB=/path/to/
 // libhiprtc.so - another one loaded beside it (e.g. the image's newer /opt/rocm/lib/libhiprtc.so, whose compiler builds the
@@ -551,38 +178,15 @@ bool jit_compile(const JitSpec& spec, std::vector<char>* code, std::string* log)
 }
 
 hipError_t jit_load(const std::vector<char>& code, JitModule* out, const JitSpec& spec) {
-  const JitKind kind = jit_kind(spec);
-  const SolvRange sv = jit_solv_range(spec.solver);  // the solver variants the translation unit holds
+  const JitEntryRow& row = kJitEntries[spec.kind];
+  const SolvRange sv = jit_entry_solvers(spec);
   hipError_t e = hipModuleLoadData(&out->module, code.data());
   if (e != hipSuccess) return e;
-  if (kind == JIT_ANALYTICAL) {  // [mode][0][LL][0]
-    for (int mode = 0; mode < 2; ++mode)
-      for (int ll = 0; ll < 2; ++ll) {
-        char name[32];
-        std::snprintf(name, sizeof name, "pmx_jit_%s_%d", mode == 0 ? "agrid" : "apair", ll);
-        e = hipModuleGetFunction(&out->fn[mode][0][ll][0], out->module, name);
-        if (e != hipSuccess) return e;
-      }
-    return hipSuccess;
-  }
-  if (kind == JIT_ODE_USER) {  // [mode][0][LL][solver]
-    for (int mode = 0; mode < 2; ++mode)
-      for (int ll = 0; ll < 2; ++ll)
-        for (int ad = sv.begin; ad < sv.end; ++ad) {
-          char name[32];
-          std::snprintf(name, sizeof name, "pmx_jit_%s_%d%d", mode == 0 ? "ugrid" : "upair", ll, ad);
-          e = hipModuleGetFunction(&out->fn[mode][0][ll][ad], out->module, name);
-          if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-  }
   for (int mode = 0; mode < 2; ++mode)
-    for (int lag = 0; lag < 2; ++lag)
+    for (int lag = 0; lag < (row.lag ? 2 : 1); ++lag)
       for (int ll = 0; ll < 2; ++ll)
-        for (int ad = sv.begin; ad < sv.end; ++ad) {
-          char name[32];
-          std::snprintf(name, sizeof name, "pmx_jit_%s_%d%d%d", mode == 0 ? "grid" : "pair", lag, ll, ad);
-          e = hipModuleGetFunction(&out->fn[mode][lag][ll][ad], out->module, name);
+        for (int solv = sv.begin; solv < sv.end; ++solv) {
+          e = hipModuleGetFunction(&out->fn[mode][lag][ll][solv], out->module, jit_entry_name(row, mode, lag, ll, solv).c_str());
           if (e != hipSuccess) return e;
         }
   return hipSuccess;

@@ -470,7 +470,7 @@ int32_t launch_jit(const pmx_model* model, const pmx_population* pop, const Devi
   const pmx::JitModule* jm = nullptr;
   const int32_t rc = jit_module(model, pop, ds, &jm);
   if (rc != PMX_OK) return rc;
-  // user analytical model: [mode][0][LL][0]; general ODE walker: [mode][0][LL][SOLV_*]
+  // (a dimension the model's kind does not have is index 0: kJitEntries, pmx_jit_source.hpp)
   const int lag = r.lag ? 1 : 0, ll = r.ll ? 1 : 0, ad = pmx::kSolvers[r.solver].solv;
   int32_t s_chunk = r.s_chunk, n_ptiles = r.n_ptiles;
   if (r.family == pmx::R_STATIC_AGRID) {

@@ -227,41 +227,36 @@ struct Resolved {
 
 int32_t spec_solver(const pmx_model_desc& d) { return d.eq_kind == PMX_EQ_ODE ? d.ode_solver : PMX_SOLVER_RK4; }  // (JitSpec::solver)
 
-// a diffeq body on the state-machine kernels (pmx_ode.hpp): theta-indexed lag / fa, at most kMaxLagSlots lagged inputs
-void take_state_machine_body(Resolved* r, std::string source, bool has_init) {
+// what every run-time-compiled model is compiled from
+void take_source(Resolved* r, pmx::JitKind kind, std::string source, uint32_t fns) {
   pmx_model* m = r->m.get();
   m->custom = true;
-  m->has_init = has_init;
   pmx::JitSpec& sp = m->jit_spec;
-  sp.nstates = m->d.nstates;
-  sp.nparams = m->d.nparams;
-  sp.nout = m->d.nout;
-  sp.ninputs = m->d.ndrugs > 0 ? m->d.ndrugs : 1;
-  sp.has_init = has_init;
-  sp.ncov = m->d.n_covariates;
-  sp.solver = spec_solver(m->d);
+  sp.kind = kind;
+  sp.desc = m->d;
   sp.source = std::move(source);
+  sp.fns = fns;
+  sp.has_init = m->has_init;
+  sp.solver = spec_solver(m->d);
   r->compiled = true;
+}
+
+// a diffeq body on the state-machine kernels (pmx_ode.hpp): theta-indexed lag / fa, at most kMaxLagSlots lagged inputs
+void take_state_machine_body(Resolved* r, std::string source, bool has_init) {
+  r->m->has_init = has_init;
+  take_source(r, pmx::JIT_ODE, std::move(source), 0);
 }
 
 // The closure walkers (pmx_analytical.hpp; pmx_ode_user.hpp, the general ODE walker, which sorts any number of lagged
 // boluses): every closure the source leaves out is generated from the descriptor.
 void take_closure_walker(Resolved* r, std::string source, uint32_t fns, bool descriptor_walker = false) {
   pmx_model* m = r->m.get();
-  m->custom = true;
   m->dyn = false;
   m->user_fns = fns;
   m->user_ode = m->d.eq_kind == PMX_EQ_ODE;
   m->user_lag = descriptor_walker || (fns & PMX_FN_ROUTE_LAG) != 0 || count_lagged(m->d) > 0;
   m->has_init = true;  // (RESET ops always carry the occasion-index flag; the policy's init may be empty)
-  pmx::JitSpec& sp = m->jit_spec;
-  sp.analytical = !m->user_ode;
-  sp.ode_user = m->user_ode;
-  sp.fns = fns;
-  sp.desc = m->d;
-  sp.solver = spec_solver(m->d);
-  sp.source = std::move(source);
-  r->compiled = true;
+  take_source(r, m->user_ode ? pmx::JIT_ODE_USER : pmx::JIT_ANALYTICAL, std::move(source), fns);
 }
 
 // A diffeq body with more than kMaxLagSlots lagged inputs leaves its path (the state-machine kernels keep four lag

@@ -1,6 +1,6 @@
 // pmx_solvers.hpp — THE solver table of the host: one row per PMX_SOLVER_* value the library accepts, with everything
 // the host knows about that solver.  The model checks (pmx_api.cpp), key_for / finish_model / plan_routes / route_name
-// (pmx_launch.cpp), the generated translation units (pmx_jit.cpp) and launch_ode (pmx_ode_builtin.hip) all read it.
+// (pmx_launch.cpp), the generated translation units (pmx_jit_source.cpp) and launch_ode (pmx_ode_builtin.hip) all read it.
 #pragma once
 
 #include <cstdint>
