@@ -64,6 +64,9 @@ typedef enum pmx_status {
 enum {
   PMX_PAIR_OK = 0,
   PMX_PAIR_COMPLEX_ROOTS = 1, /* reference panics: two_compartment_models.rs:20-22, three_compartment_models.rs:32-34 */
+                              /* (set at the subject's first propagation, where the reference's solve runs: rows from there to the
+                                 occasion's end are NaN, rows in front of an occasion's first propagation are served as usual, a
+                                 subject that never propagates stays PMX_PAIR_OK; a failed pair's log-likelihood is NaN) */
   PMX_PAIR_NONFINITE = 2,     /* a prediction is NaN/inf (PharmsolError::NonFiniteLikelihood-style guard) */
   PMX_PAIR_BAD_LAG = 3,       /* the support point gives a NaN lag time: its predictions are NaN (the reference panics in
                                  its sort).  A NEGATIVE lag is not an error: the bolus moves earlier, as in the reference
@@ -340,6 +343,11 @@ void pmx_model_destroy(pmx_model* model);
  *   theta  [n_support x nparams] row-major (ParameterOrder::matrix rows, matrix.rs:62-65)
  *   pred   [n_observations x ld_pred]
  *   status [n_subjects x n_support] bytes (PMX_PAIR_*), may be NULL
+ * What a caller owns, for this and every other entry point that takes such buffers (pmx_loglik: ll in place of pred):
+ *   - pred, ll, status and theta need only their natural alignment: 8 bytes for the doubles, 1 byte for status;
+ *   - the last row needs n_support elements, not ld;
+ *   - nothing outside [row * ld, row * ld + n_support) is written (tests/test_gpu_output_contract.py);
+ *   - a NULL status is never dereferenced.
  * Host-pointer form: copies theta in and pred/status out (PCIe inclusive). */
 int32_t pmx_predict(const pmx_model* model, const pmx_population* pop, const double* theta, int64_t n_support,
                     double* pred, int64_t ld_pred, uint8_t* status);

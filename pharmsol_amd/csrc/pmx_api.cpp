@@ -369,17 +369,30 @@ int64_t pmx_recommended_ld(int64_t n_support) { return n_support <= 0 ? 0 : (n_s
 int32_t pmx_measure_write_ceiling(double* d_buf, int64_t n_doubles, int32_t reps, void* stream, double* gb_per_s) {
   g_err.clear();
   if (!d_buf || !gb_per_s || n_doubles < 2 || reps < 1) return fail(PMX_ERR_INVALID_ARGUMENT, "bad argument");
+  // events and launches belong on the buffer's device, whichever one is current in the caller
+  DeviceGuard guard;
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, d_buf) == hipSuccess) {
+    PMX_HIP(guard.enter(attr.device));
+  } else {
+    (void)hipGetLastError();  // (a pointer the runtime cannot place: stay on the current device)
+  }
+  // The fills store 16 bytes per lane: an odd n_doubles leaves one double behind them.  One 8-byte store writes it,
+  // outside the timed loops: with each shape's untimed first fill, and once more after the last timed repetition.
+  double* const tail = (n_doubles & 1) ? d_buf + (n_doubles - 1) : nullptr;
   StreamTimer timer(stream);
   hipError_t e = hipSuccess;
   float best_ms = 0.0f;
   for (int shape = 0; shape < 4 && e == hipSuccess; ++shape) {  // the best of four store shapes (pmx_util.hip)
     e = pmx::launch_fill_linear(d_buf, n_doubles, 0.0, stream, shape);  // untimed
+    if (e == hipSuccess && tail) e = pmx::launch_fill_one(tail, 0.0, stream);
     if (e == hipSuccess) e = timer.start();
     for (int32_t i = 0; i < reps && e == hipSuccess; ++i) e = pmx::launch_fill_linear(d_buf, n_doubles, 0.0, stream, shape);
     float ms = 0.0f;
     if (e == hipSuccess) e = timer.stop(&ms);
     if (e == hipSuccess && (shape == 0 || ms < best_ms)) best_ms = ms;
   }
+  if (e == hipSuccess && tail) e = pmx::launch_fill_one(tail, 0.0, stream);
   if (e != hipSuccess) return fail(PMX_ERR_HIP, hipGetErrorString(e));
   *gb_per_s = static_cast<double>(n_doubles / 2 * 16) * reps / (static_cast<double>(best_ms) * 1.0e-3) / 1.0e9;
   return PMX_OK;

@@ -109,7 +109,10 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
   const bool any_half = __any(pair_half ? 1 : 0) != 0;
 
   typename LM::S::Coef coef;
-  double inv_vol0;  // 1/volume of output 0 (NaN for a lane with complex roots: all its predictions are NaN)
+  // 1/volume of output 0.  A lane with complex roots has NaN coefficients (lane_setup): its rows are NaN from an occasion's
+  // first PROP on, like every walker's.  Its log-likelihood sum is NaN as a whole (a failed pair has no sum), and every
+  // class program propagates (pmx_plan.cpp build_class_plan), so the pair is PMX_PAIR_COMPLEX_ROOTS.
+  double inv_vol0;
   bool lane_good;
   LM Ld;  // DYNC: the lane's base parameters, kept for the per-member rebuilds
   if constexpr (DYNC) {
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
     lane_setup<KID, false>(m, theta + pc * m.nparams, L);
     coef = L.coef;
     lane_good = L.ok;
-    inv_vol0 = L.ok ? L.inv_vol[0] : __longlong_as_double(0x7ff8000000000000LL);
+    inv_vol0 = (L.ok || !LL) ? L.inv_vol[0] : __longlong_as_double(0x7ff8000000000000LL);
   }
   (void)Ld;
   double lagv = 0.0;      // LAGC: this lane's lag time of the lagged input
@@ -405,7 +408,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
           if (vp >= 0) v = th[vp];  // (scalar condition)
           double iv = 1.0 / v;
           asm volatile("" : "+v"(iv));
-          inv_vol = (lane_good && !lane_badlag) ? iv : __longlong_as_double(0x7ff8000000000000LL);
+          inv_vol = ((lane_good || !LL) && !lane_badlag) ? iv : __longlong_as_double(0x7ff8000000000000LL);
         }
         if constexpr (LL) {
           // fold the G predictions into the members' sums instead of storing them (ll_accumulate, per member;

@@ -37,7 +37,11 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
 
   LM L;
   lane_setup<KID, DYN>(m, th, L);
-  uint8_t st_lane0 = L.ok ? PMX_PAIR_OK : PMX_PAIR_COMPLEX_ROOTS;
+  // A lane with complex eigenvalues (lane_setup: all its coefficients are NaN) fails a subject at its first PROP, where
+  // the reference's solve panics: the state is NaN from there to the occasion's end, the pair stays failed.  Up to an
+  // occasion's first PROP the lane serves the subject like any other.  (The covariate walkers decide per segment.)
+  const bool lane_cplx = !DYN && !L.ok;
+  uint8_t st_lane0 = PMX_PAIR_OK;
   LagState ls;
   if constexpr (LAG) {
 #pragma unroll
@@ -133,13 +137,18 @@ __global__ __launch_bounds__(kBlock, (!LAG && LaneModel<KID>::NS <= 2) ? 4 : ((!
           }
           step_from_exps<LM::ST>(L.coef, ex, x, r);
         }
+        if (lane_cplx) {  // (DYN: never)
+          st = PMX_PAIR_COMPLEX_ROOTS;
+#pragma unroll
+          for (int i = 0; i < NS; ++i) x[i] = nanv;
+        }
         xpad = 0.0;  // pm_* wrappers re-pad slot 0 with 0 after every kernel call (analytical/mod.rs:70-75)
       } else if (kind == OP_OBS) {
         if constexpr (LAG) {  // no PROP step in front of this observation: lagged boluses may land before it (bit 31)
           if (meta >> kOpFlushShift) lag_flush_before<NS>(m, ops, ls, a, th, x);
         }
         double y = lane_out<KID>(m, L, x, xpad, io, cov);
-        if (st == PMX_PAIR_COMPLEX_ROOTS || st == PMX_PAIR_BAD_LAG) y = nanv;
+        if ((DYN && st == PMX_PAIR_COMPLEX_ROOTS) || st == PMX_PAIR_BAD_LAG) y = nanv;  // (not DYN: the state is NaN)
         if constexpr (LL) {
           ll_accumulate(as_const(ops.ll_obs) + row * 4, y, ll_acc);  // row is wave-uniform: scalar fetches
         } else {

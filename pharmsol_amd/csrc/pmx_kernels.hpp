@@ -143,7 +143,9 @@ hipError_t launch_ll_prepare(const LLPrepareArgs& a);
 hipError_t launch_status_any(const uint8_t* d_status, int64_t n, int32_t* d_flag, void* stream);
 
 // a linear streaming fill of n_doubles (pmx_measure_write_ceiling)
+// (16 bytes per lane: the n_doubles / 2 pairs; the last double of an odd n_doubles is launch_fill_one's)
 hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape = 0);  // shape 0..3 (pmx_util.hip)
+hipError_t launch_fill_one(double* d_dst, double v, void* stream);  // *d_dst = v, one 8-byte store
 
 // One entry per kernel family, at the end of the family's translation unit (pmx_grid.hip, pmx_classed.hip, ...): it
 // switches on the model's kernel id and the route's variant flags and enqueues that instantiation.  Policy-free: which

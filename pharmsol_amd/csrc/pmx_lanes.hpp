@@ -115,6 +115,21 @@ __device__ __forceinline__ void lane_setup(const DevModel& m, const double* __re
     double q[LM::NKP];
     to_native_params<KID>(L.kp_base, q);
     L.ok = LM::S::prepare(q, L.coef);
+    // THE rule for a support point with complex eigenvalues, the same on every route of a plain or lagged model: the
+    // reference panics inside a solve, and the oracle turns the state into NaN there (pmx_oracle.c, simulate_event).  So
+    // such a lane's coefficients are all NaN: whatever a PROP builds from them makes the state NaN, the rows behind it are
+    // NaN, and the rows in front of an occasion's first PROP (RESET starts from a finite state) are served like any
+    // other lane's.  The pair is PMX_PAIR_COMPLEX_ROOTS once it has propagated.
+    if (!L.ok) {
+      using Coef = typename LM::S::Coef;  // (doubles and nothing else: pmx_structures.hpp)
+      static_assert(std::is_trivially_copyable<Coef>::value && alignof(Coef) == alignof(double) && sizeof(Coef) % sizeof(double) == 0,
+                    "a structure's coefficients are a plain block of doubles");
+      constexpr int kN = static_cast<int>(sizeof(Coef) / sizeof(double));
+      double nans[kN];
+#pragma unroll
+      for (int i = 0; i < kN; ++i) nans[i] = __longlong_as_double(0x7ff8000000000000LL);
+      __builtin_memcpy(&L.coef, nans, sizeof(Coef));
+    }
   }
 }
 

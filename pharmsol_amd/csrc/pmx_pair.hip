@@ -25,7 +25,11 @@ __global__ __launch_bounds__(kBlock) void pmx_analytical_pair(DevModel m, DevOps
 
   LM L;
   lane_setup<KID, DYN>(m, th, L);
-  uint8_t st_lane0 = L.ok ? PMX_PAIR_OK : PMX_PAIR_COMPLEX_ROOTS;
+  // A lane with complex eigenvalues (lane_setup: all its coefficients are NaN) fails a subject at its first PROP, where
+  // the reference's solve panics: the state is NaN from there to the occasion's end, the pair stays failed.  Up to an
+  // occasion's first PROP the lane serves the subject like any other.  (The covariate walkers decide per segment.)
+  const bool lane_cplx = !DYN && !L.ok;
+  uint8_t st_lane0 = PMX_PAIR_OK;
   LagState ls;
   if constexpr (LAG) {
 #pragma unroll
@@ -79,13 +83,18 @@ __global__ __launch_bounds__(kBlock) void pmx_analytical_pair(DevModel m, DevOps
         } else {
           advance<LM::ST>(L.coef, x, a, r);
         }
+        if (lane_cplx) {  // (DYN: never)
+          st = PMX_PAIR_COMPLEX_ROOTS;
+#pragma unroll
+          for (int i = 0; i < NS; ++i) x[i] = nanv;
+        }
         xpad = 0.0;
       } else if (kind == OP_OBS) {
         if constexpr (LAG) {  // (see the GRID kernel)
           if (meta >> kOpFlushShift) lag_flush_before<NS>(m, ops, ls, a, th, x);
         }
         double y = lane_out<KID>(m, L, x, xpad, io, cov);
-        if (st == PMX_PAIR_COMPLEX_ROOTS || st == PMX_PAIR_BAD_LAG) y = nanv;
+        if ((DYN && st == PMX_PAIR_COMPLEX_ROOTS) || st == PMX_PAIR_BAD_LAG) y = nanv;  // (not DYN: the state is NaN)
         if constexpr (LL) {
           ll_accumulate(ops.ll_obs + row * 4, y, ll_acc);
         } else {

@@ -359,7 +359,11 @@ void build_class_plan(const HostPopulation& hp, const OpStream& os, int32_t G, i
   std::vector<int32_t> candidates;
   for (int64_t s = 0; s < hp.n_subjects; ++s) {
     // an empty subject: nothing to compute, but the generic walker still owns its status bytes
-    const bool generic = os.subj_op_off[s + 1] == os.subj_op_off[s] || (os.key.rate_input == 1 && doses_into_pad(os, s));
+    // ... and so does one that never propagates: the classed kernels fail every member of a lane with complex eigenvalues,
+    // which is the walkers' rule (fail at the first PROP) only for programs that have one
+    bool propagates = false;
+    for (int64_t o = os.subj_op_off[s]; o < os.subj_op_off[s + 1] && !propagates; ++o) propagates = op_kind(os.op_meta[o]) == OP_PROP;
+    const bool generic = !propagates || (os.key.rate_input == 1 && doses_into_pad(os, s));
     (generic ? cp->generic_subjects : candidates).push_back(static_cast<int32_t>(s));
   }
   const Classes exact = group_subjects(

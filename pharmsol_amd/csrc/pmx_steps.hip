@@ -33,8 +33,12 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
 
   LM L;
   lane_setup<KID, false>(m, th, L);
-  const uint8_t st_lane = L.ok ? PMX_PAIR_OK : PMX_PAIR_COMPLEX_ROOTS;
-  const double inv_vol0 = L.ok ? L.inv_vol[0] : nanv;  // (a lane with complex roots: every prediction NaN)
+  // A lane with complex eigenvalues (lane_setup: all its coefficients are NaN) fails a subject at its first PROP and
+  // serves it like any other lane up to there.  Whether a subject propagated is read off the lane's exponentials
+  // afterwards: they are cleared per subject (a subject's first PROP starts a fresh ladder, pmx_compile.cpp
+  // code_ladder) and are NaN after any PROP of such a lane (tests/test_gpu_output_contract.py holds every structure
+  // to it).  A flag set in the PROP branch cost the walk 2.5 %.
+  const double inv_vol0 = L.inv_vol[0];
   const int out_state0 = m.out[0].state;
   double ex[LM::S::NE];  // the lane's exponentials of the last PROP (ladder)
 #pragma unroll
@@ -56,6 +60,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
 #pragma unroll
     for (int i = 0; i < NS; ++i) x[i] = 0.0;
     double ll_acc = 0.0, nanacc = 0.0;
+    ex[0] = 0.0;
     if (zero_status == 1 && status != nullptr) {  // (see pmx_analytical_grid)
       const uint32_t zl = threadIdx.x & 63u;
       const int64_t zp = static_cast<int64_t>(ptile) * tile + (threadIdx.x & ~63u) + 8 * zl;
@@ -105,7 +110,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
           if (vp >= 0) v = th[vp];
           double iv = 1.0 / v;
           asm volatile("" : "+v"(iv));
-          inv_vol = L.ok ? iv : nanv;
+          inv_vol = iv;
         }
         double xs = x[0];
 #pragma unroll
@@ -121,7 +126,7 @@ __global__ __launch_bounds__(kBlock, (LaneModel<KID>::NS <= 2) ? 4 : 2) void pmx
         }
       }
     }
-    uint8_t st = st_lane;
+    uint8_t st = (!L.ok && ex[0] != ex[0]) ? PMX_PAIR_COMPLEX_ROOTS : PMX_PAIR_OK;
     if constexpr (LL) {
       if (st == PMX_PAIR_OK && !isfinite(ll_acc)) st = PMX_PAIR_NONFINITE;  // NonFiniteLikelihood (prediction.rs:119-124)
       if (lane_ok) ops.ll_out[s * ops.ll_ld + p] = (st == PMX_PAIR_OK || st == PMX_PAIR_NONFINITE) ? ll_acc : nanv;

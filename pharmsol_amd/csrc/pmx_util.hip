@@ -192,7 +192,14 @@ __global__ __launch_bounds__(256) void pmx_fill_linear(double* __restrict__ dst,
     }
   }
 }
+
+__global__ void pmx_fill_one(double* dst, double v) { *dst = v; }
 }  // namespace
+
+hipError_t launch_fill_one(double* d_dst, double v, void* stream) {
+  hipLaunchKernelGGL(pmx_fill_one, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), d_dst, v);
+  return hipGetLastError();
+}
 
 hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape) {
   const int64_t n_pairs = n_doubles / 2;
