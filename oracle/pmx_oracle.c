@@ -1013,6 +1013,7 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
   uint8_t st = PMX_PAIR_OK;
   adapt_t adapt = {m->rk4_h_max, 0}; /* adaptive solver: the proposal restarts with every subject */
   int coarse = 0;                    /* checked RK4: some piece's probe has failed */
+  int bad_lag = 0;                   /* some bolus' landing time is NaN */
   ctx_t ctx;
   ctx.m = m;
   ctx.theta = theta;
@@ -1071,14 +1072,22 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
           g_user_lag(ev[i].time, 0, theta, m->n_covariates ? cv : 0, 0, (g_user_mask & PMX_FN_DERIVE) ? der : 0, lagv);
           double l = input < PMX_MAX_INPUTS ? lagv[input] : 0.0;
           if (l != 0.0) {
-            ev[i].time += l;
-            shifted = 1;
+            if (ev[i].time + l != ev[i].time + l) {
+              bad_lag = 1; /* a NaN time: the reference panics in solve's sort (analytical/mod.rs:326); the bolus stays put */
+            } else {
+              ev[i].time += l;
+              shifted = 1;
+            }
           }
         } else if (input < PMX_MAX_INPUTS && m->lag_param[input] >= 0) {
           double l = theta[m->lag_param[input]];
           if (l != 0.0) {
-            ev[i].time += l;
-            shifted = 1;
+            if (ev[i].time + l != ev[i].time + l) {
+              bad_lag = 1;
+            } else {
+              ev[i].time += l;
+              shifted = 1;
+            }
           }
         }
       }
@@ -1219,6 +1228,10 @@ static int simulate_pair(const pmx_model_desc* m, const pmx_population_desc* pop
         }
       }
     }
+  }
+  if (bad_lag) { /* PMX_PAIR_BAD_LAG: every prediction of the pair is NaN (include/pmx.h) */
+    st = PMX_PAIR_BAD_LAG;
+    for (int64_t r = 0; r < row; r++) pred[r * pred_stride] = NAN;
   }
   if (status) *status = st;
   return PMX_OK;
@@ -1563,7 +1576,7 @@ int32_t pmx_oracle_loglik(const pmx_model_desc* model, const pmx_population_desc
           total += term;
         }
         if (st == PMX_PAIR_OK && !isfinite(total)) st = PMX_PAIR_NONFINITE; /* NonFiniteLikelihood, prediction.rs:119-124 */
-        if (st == PMX_PAIR_COMPLEX_ROOTS) total = NAN;
+        if (st == PMX_PAIR_COMPLEX_ROOTS || st == PMX_PAIR_BAD_LAG) total = NAN;
         ll[s * ld_ll + p] = total;
         if (status) status[s * n_support + p] = st;
         if (st) {
