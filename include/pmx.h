@@ -587,6 +587,39 @@ int32_t pmx_loglik_batch(const pmx_model* model, const pmx_population* pop, cons
 int32_t pmx_loglik_batch_device(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em,
                                 const double* d_theta, double* d_ll, uint8_t* d_status, void* stream);
 
+/* The two reductions NPAG and NPOD take of the matrix pmx_loglik writes, computed where the matrix is, in the log domain
+ * (the plain psi = exp(ll) underflows for a subject with some 70 observations, likelihood/matrix.rs:127-150):
+ *   lpyl[s] = ln sum_{p: w[p] > 0} w[p] exp(ll[s][p])     the mixture log-likelihood of subject s; NPAG's objective is its
+ *                                                         sum over subjects
+ *   D[p]    = sum_s exp(ll[s][p] - lpyl[s]) - n_subjects  the D-function of candidate p: ParameterOptimizer::cost returns
+ *                                                         -D of one point (optimize/parameters.rs:30-52)
+ * Edges.  A column with w[p] == 0 is skipped whatever it holds (a failed support point that carries no weight poisons
+ * nobody); ll = -inf adds 0; a row whose weighted entries are all -inf gives -inf; a NaN under positive weight gives
+ * NaN; a negative or NaN weight gives NaN in every row (device form) or is refused (host form).  D follows IEEE like the
+ * reference's p_i / pyl_i: lpyl[s] = -inf with a finite ll gives +inf, -inf - (-inf) gives NaN, an exp that overflows
+ * gives +inf.
+ * Both are summed in a fixed order: a result is bit-identical from run to run, for any alignment and any ld.
+ * Sharding by subjects needs nothing more: each rank's D subtracts its own subject count, so the ranks' D vectors add.
+ *
+ * Device forms: pure reductions of a matrix pmx_loglik_device wrote (d_ll, ld_ll as there; 8-byte alignment is all any
+ * pointer needs); stream-ordered, not synchronised.  d_scratch: pmx_dfunction_scratch_doubles(n_subjects, n_cand)
+ * doubles the caller owns for the length of the call on `stream` (two calls on different streams need two). */
+int32_t pmx_mixture_loglik_device(const pmx_population* pop, const double* d_ll, int64_t n_support, int64_t ld_ll,
+                                  const double* d_w /*[n_support]*/, double* d_lpyl /*[n_subjects]*/, void* stream);
+int64_t pmx_dfunction_scratch_doubles(int64_t n_subjects, int64_t n_cand); /* needs no device; <= 0 arguments: -1 */
+int32_t pmx_dfunction_device(const pmx_population* pop, const double* d_ll, int64_t n_cand, int64_t ld_ll,
+                             const double* d_lpyl /*[n_subjects]*/, double* d_scratch, double* d_D /*[n_cand]*/,
+                             void* stream);
+/* Host forms: theta in, n_subjects resp. n_cand doubles out; the matrix never crosses the link.  Errors and status as
+ * for pmx_loglik: with failed pairs the call returns PMX_ERR_PAIR_FAILED, the status array (if given) is filled and the
+ * outputs are still copied out.  pmx_mixture_loglik refuses (PMX_ERR_INVALID_ARGUMENT) a w that holds a negative or NaN
+ * entry, or no positive one. */
+int32_t pmx_mixture_loglik(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em,
+                           const double* theta, int64_t n_support, const double* w, double* lpyl,
+                           uint8_t* status /*[n_subjects x n_support] or NULL*/);
+int32_t pmx_dfunction(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
+                      int64_t n_cand, const double* lpyl, double* D, uint8_t* status /*[n_subjects x n_cand] or NULL*/);
+
 /* Row pitch (ld_pred, in doubles) at which the prediction kernels write fastest: n_support rounded up to a multiple of 16,
  * so every row starts on a 128-byte boundary.  Measured on C3 (profiles/r03/ld_by_allocation.txt): 1000 -> 1008 doubles
  * gives 6.45 -> 6.8 TB/s in fast allocations and 5.3 -> 5.5 in slow ones; a pitch that is a multiple of 8 but not 16

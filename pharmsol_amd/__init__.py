@@ -13,6 +13,7 @@ from .equation import (ODE, Analytical, Equation, LabelError, Lin, Pow, Ratio, R
                        infusion, ode)
 from .error_model import AssayErrorModel, AssayErrorModels, ErrorPoly, ResidualErrorModel, ResidualErrorModels
 from .flatten import FlatPopulation, flatten
+from .optimize import ParameterOptimizer, create_initial_simplex
 from .parameters import ParameterError, ParameterOrder, Parameters
 from .pmetrics import DataError, DataRow, build_data, read_pmetrics
 from .predictions import PopulationPredictions, Prediction, SubjectPredictions
@@ -22,5 +23,6 @@ __all__ = [
     "Bolus", "Censor", "Covariates", "Data", "DataError", "DataRow", "build_data", "read_pmetrics", "interpolate", "Event", "Infusion", "Observation", "Occasion", "Subject", "SubjectBuilder",
     "ODE", "Analytical", "Equation", "LabelError", "Lin", "Pow", "Ratio", "Route", "Scaled", "analytical", "bolus",
     "infusion", "ode", "AssayErrorModel", "AssayErrorModels", "ErrorPoly", "ResidualErrorModel", "ResidualErrorModels", "FlatPopulation", "flatten",
+    "ParameterOptimizer", "create_initial_simplex",
     "Parameters", "ParameterOrder", "ParameterError", "Prediction", "SubjectPredictions", "PopulationPredictions", "PmxError",
 ]

@@ -258,6 +258,32 @@ int32_t pmx_loglik_batch_device(const pmx_model* model, const pmx_population* cp
   return enqueue(model, c.pop, d_theta, 1, 1, d_ll, 1, d_status, stream, &req);
 }
 
+// the reductions of a matrix pmx_loglik_device wrote (pmx_mixture.hip)
+int32_t pmx_mixture_loglik_device(const pmx_population* cpop, const double* d_ll, int64_t n_support, int64_t ld_ll,
+                                  const double* d_w, double* d_lpyl, void* stream) {
+  DeviceCall c;
+  const int32_t rc = c.begin(cpop, {{cpop && d_ll && d_w && d_lpyl, kNull},
+                                    {matrix_ok(n_support, ld_ll), "n_support must be > 0 and ld_ll >= n_support"}});
+  if (rc != PMX_OK) return rc;
+  PMX_HIP(pmx::launch_mixture_rows(d_ll, c.pop->hp.n_subjects, n_support, ld_ll, d_w, d_lpyl, stream));
+  return PMX_OK;
+}
+
+int64_t pmx_dfunction_scratch_doubles(int64_t n_subjects, int64_t n_cand) {
+  if (n_subjects <= 0 || n_cand <= 0) return -1;
+  return pmx::dfunction_tiles(n_subjects, n_cand) * n_cand;
+}
+
+int32_t pmx_dfunction_device(const pmx_population* cpop, const double* d_ll, int64_t n_cand, int64_t ld_ll,
+                             const double* d_lpyl, double* d_scratch, double* d_D, void* stream) {
+  DeviceCall c;
+  const int32_t rc = c.begin(cpop, {{cpop && d_ll && d_lpyl && d_scratch && d_D, kNull},
+                                    {matrix_ok(n_cand, ld_ll), "n_cand must be > 0 and ld_ll >= n_cand"}});
+  if (rc != PMX_OK) return rc;
+  PMX_HIP(pmx::launch_dfunction(d_ll, c.pop->hp.n_subjects, n_cand, ld_ll, d_lpyl, d_scratch, d_D, stream));
+  return PMX_OK;
+}
+
 int32_t pmx_time_predict_device(const pmx_model* model, const pmx_population* cpop, const double* d_theta,
                                 int64_t n_support, double* d_pred, int64_t ld_pred, int32_t reps, void* stream,
                                 double* ms_per_pass) {

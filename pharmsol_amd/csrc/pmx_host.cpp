@@ -1,5 +1,5 @@
 // pmx_host.cpp — the HOST-pointer entry points of include/pmx.h: pmx_predict, pmx_predict_batch, pmx_loglik,
-// pmx_loglik_batch.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
+// pmx_loglik_batch, pmx_mixture_loglik, pmx_dfunction.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
 // result out.
 #include <cstring>
 #include <limits>
@@ -15,8 +15,9 @@ struct HostWorkspace {
   void* d_theta = nullptr;
   void* d_out = nullptr;
   void* d_status = nullptr;
+  void* d_red = nullptr;      // the reductions' small vectors: weights or lpyl in, lpyl or D out, the D-function's slabs
   int32_t* d_flag = nullptr;  // "any pair failed" (pmx_status_any)
-  size_t theta_cap = 0, out_cap = 0, status_cap = 0;
+  size_t theta_cap = 0, out_cap = 0, status_cap = 0, red_cap = 0;
   static constexpr size_t kBounce = 32u << 20;
   void* bounce[2] = {nullptr, nullptr};
   hipEvent_t bev[2] = {nullptr, nullptr};
@@ -25,6 +26,7 @@ struct HostWorkspace {
     if (d_theta) (void)hipFree(d_theta);
     if (d_out) (void)hipFree(d_out);
     if (d_status) (void)hipFree(d_status);
+    if (d_red) (void)hipFree(d_red);
     if (d_flag) (void)hipFree(d_flag);
     for (int i = 0; i < 2; ++i) {
       if (bounce[i]) (void)hipHostFree(bounce[i]);
@@ -229,14 +231,11 @@ int32_t predict_host(const pmx_model* model, const pmx_population* cpop, const d
   return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
 }
 
-// ll[s][p] (matrix shape) or ll[s] (batch shape: subject s with theta row s, likelihood/mod.rs:119-177)
-int32_t loglik_host(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em, const double* theta,
-                    int64_t P, int batch, double* ll, int64_t ld_ll, uint8_t* status) {
-  pmx::clear_error();
-  if (!model || !cpop || !em || !theta || !ll) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
-  if (!batch && (P <= 0 || ld_ll < P)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0 and ld_ll >= n_support");
-  pmx_population* pop = const_cast<pmx_population*>(cpop);
-  HostCall call;
+// The log-likelihood part every host form shares: begin, the kernels, and the invalid-sigma counter read back.  On
+// PMX_OK call.d_out() holds ll[s][p] (matrix shape, dense) or ll[s] (batch shape: subject s with theta row s,
+// likelihood/mod.rs:119-177) on the device, ordered on call.ws->compute.
+int32_t loglik_on_device(HostCall& call, const pmx_model* model, pmx_population* pop, const pmx_error_model* em,
+                         const double* theta, int64_t P, int batch) {
   int32_t rc = call.begin(model, pop, theta, P, batch, pop->hp.n_subjects);
   if (rc != PMX_OK) return rc;
   HostWorkspace* ws = call.ws;
@@ -250,6 +249,19 @@ int32_t loglik_host(const pmx_model* model, const pmx_population* cpop, const pm
     if (n_bad > 0)
       return fail(PMX_ERR_ERROR_MODEL, "NegativeSigma / NonFiniteSigma for " + std::to_string(n_bad) + " observation(s)");
   }
+  return PMX_OK;
+}
+
+int32_t loglik_host(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em, const double* theta,
+                    int64_t P, int batch, double* ll, int64_t ld_ll, uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !cpop || !em || !theta || !ll) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!batch && (P <= 0 || ld_ll < P)) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0 and ld_ll >= n_support");
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  HostCall call;
+  int32_t rc = loglik_on_device(call, model, pop, em, theta, P, batch);
+  if (rc != PMX_OK) return rc;
+  HostWorkspace* ws = call.ws;
   bool any_failed = false;
   if ((rc = call.finish(status, ll, ld_ll, &any_failed)) != PMX_OK) return rc;
   if (!any_failed) return PMX_OK;
@@ -261,6 +273,31 @@ int32_t loglik_host(const pmx_model* model, const pmx_population* cpop, const pm
   for (size_t i = 0; i < call.n_status; ++i)
     if (hst[i] != PMX_PAIR_OK) ll[i] = -std::numeric_limits<double>::infinity();
   return PMX_OK;
+}
+
+// A reduction of the matrix a host form left on the device (pmx_mixture.hip): `in` [n_in] goes up, the kernels run on
+// the workspace's [n_in | n_out | n_scratch] doubles, `out` [n_out] comes back - with the status flag (and array) of
+// pmx_loglik; the matrix never crosses the link.
+template <class Launch>
+int32_t reduce_host(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em, const double* theta,
+                    int64_t P, const double* in, int64_t n_in, double* out, int64_t n_out, int64_t n_scratch,
+                    uint8_t* status, Launch&& launch) {
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  HostCall call;
+  int32_t rc = loglik_on_device(call, model, pop, em, theta, P, 0);
+  if (rc != PMX_OK) return rc;
+  HostWorkspace* ws = call.ws;
+  if ((rc = ws_reserve(&ws->d_red, &ws->red_cap, static_cast<size_t>(n_in + n_out + n_scratch) * sizeof(double))) != PMX_OK)
+    return rc;
+  double* d_in = static_cast<double*>(ws->d_red);
+  double* d_res = d_in + n_in;
+  PMX_HIP(hipMemcpyAsync(d_in, in, static_cast<size_t>(n_in) * sizeof(double), hipMemcpyHostToDevice, ws->compute));
+  PMX_HIP(launch(call.d_out(), d_in, d_res, d_res + n_out, ws->compute));
+  bool any_failed = false;
+  if ((rc = ws_finish_status(ws, status, call.n_status, &any_failed)) != PMX_OK) return rc;
+  const size_t out_bytes = static_cast<size_t>(n_out) * sizeof(double);
+  if ((rc = ws_copy_out(ws, out, out_bytes, d_res, out_bytes, 1)) != PMX_OK) return rc;
+  return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
 }
 
 }  // namespace
@@ -282,6 +319,37 @@ int32_t pmx_loglik(const pmx_model* model, const pmx_population* pop, const pmx_
 int32_t pmx_loglik_batch(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
                          double* ll, uint8_t* status) {
   return loglik_host(model, pop, em, theta, 1, 1, ll, 1, status);
+}
+
+int32_t pmx_mixture_loglik(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
+                           int64_t n_support, const double* w, double* lpyl, uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !pop || !em || !theta || !w || !lpyl) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_support <= 0) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0");
+  bool any_positive = false;
+  for (int64_t p = 0; p < n_support; ++p) {
+    if (!(w[p] >= 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "w[" + std::to_string(p) + "] is negative or NaN");
+    any_positive = any_positive || w[p] > 0.0;
+  }
+  if (!any_positive) return fail(PMX_ERR_INVALID_ARGUMENT, "w holds no positive entry");
+  const int64_t S = pop->hp.n_subjects;
+  return reduce_host(model, pop, em, theta, n_support, w, n_support, lpyl, S, 0, status,
+                     [&](const double* d_ll, const double* d_w, double* d_lpyl, double*, hipStream_t st) {
+                       return pmx::launch_mixture_rows(d_ll, S, n_support, n_support, d_w, d_lpyl, st);
+                     });
+}
+
+int32_t pmx_dfunction(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
+                      int64_t n_cand, const double* lpyl, double* D, uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !pop || !em || !theta || !lpyl || !D) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_cand <= 0) return fail(PMX_ERR_INVALID_ARGUMENT, "n_cand must be > 0");
+  const int64_t S = pop->hp.n_subjects;
+  const int64_t n_scratch = S > 0 ? pmx::dfunction_tiles(S, n_cand) * n_cand : 0;
+  return reduce_host(model, pop, em, theta, n_cand, lpyl, S, D, n_cand, n_scratch, status,
+                     [&](const double* d_ll, const double* d_lpyl, double* d_D, double* d_scratch, hipStream_t st) {
+                       return pmx::launch_dfunction(d_ll, S, n_cand, n_cand, d_lpyl, d_scratch, d_D, st);
+                     });
 }
 
 }  // extern "C"

@@ -147,6 +147,28 @@ hipError_t launch_status_any(const uint8_t* d_status, int64_t n, int32_t* d_flag
 hipError_t launch_fill_linear(double* d_dst, int64_t n_doubles, double v, void* stream, int shape = 0);  // shape 0..3 (pmx_util.hip)
 hipError_t launch_fill_one(double* d_dst, double v, void* stream);  // *d_dst = v, one 8-byte store
 
+// The reductions of a log-likelihood matrix ll[S][ld] (pmx_mixture.hip).
+//   lpyl[s] = ln sum_{p: w[p] > 0} w[p] exp(ll[s][p]); a wave owns a row up to kMixtureWaveRowMax columns, a block beyond
+constexpr int64_t kMixtureWaveRowMax = 1024;
+hipError_t launch_mixture_rows(const double* d_ll, int64_t S, int64_t P, int64_t ld, const double* d_w, double* d_lpyl,
+                               void* stream);
+//   D[p] = sum_s exp(ll[s][p] - lpyl[s]) - S, in two launches: partial sums of row tiles into d_scratch[n_tiles][n_cand],
+//   then the tiles added in order.  A tile is what one wave sums: kDfunctionPasses passes over 64 columns x 1 row, or -
+//   n_cand <= 32 - over (1 << cshift) columns x (64 >> cshift) rows.  Pure host arithmetic, shared with
+//   pmx_dfunction_scratch_doubles:
+constexpr int64_t kDfunctionPasses = 64;
+inline int dfunction_cshift(int64_t n_cand) {  // log2 of the columns a wave spans
+  int c = 0;
+  while (c < 6 && (int64_t{1} << c) < n_cand) ++c;
+  return c;
+}
+inline int64_t dfunction_tiles(int64_t S, int64_t n_cand) {
+  const int64_t rows = kDfunctionPasses * (64 >> dfunction_cshift(n_cand));
+  return (S + rows - 1) / rows;
+}
+hipError_t launch_dfunction(const double* d_ll, int64_t S, int64_t n_cand, int64_t ld, const double* d_lpyl,
+                            double* d_scratch, double* d_D, void* stream);
+
 // One entry per kernel family, at the end of the family's translation unit (pmx_grid.hip, pmx_classed.hip, ...): it
 // switches on the model's kernel id and the route's variant flags and enqueues that instantiation.  Policy-free: which
 // family, which variant and which geometry is the route's (pmx_launch.cpp plan_routes).

@@ -6,6 +6,7 @@
 //   pmx_classed.hip  pmx_classed_ll.hip                          the classed kernels
 //   pmx_ode_builtin.hip                                          built-in ODE bodies (walkers and steppers: pmx_ode.hpp)
 //   pmx_util.hip                                                 log-likelihood tables, status scan, streaming fill
+//   pmx_mixture.hip                                              reductions of the log-likelihood matrix: mixture rows, D-function
 //
 // One wavefront lane per (subject, support point) pair, two lane mappings:
 //

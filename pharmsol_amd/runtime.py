@@ -399,6 +399,59 @@ def loglik(model, pop: DevicePopulation, error_models, theta, ll=None, status=No
     return ll, status
 
 
+def _ll_matrix(pop: DevicePopulation, ll):
+    """``(n_columns, ld)`` of a log-likelihood matrix ``[n_subjects, n_columns]`` whose rows are contiguous."""
+    assert ll.is_cuda and ll.dtype.is_floating_point and ll.element_size() == 8 and ll.dim() == 2
+    assert ll.shape[0] == pop.n_subjects and ll.stride(1) == 1
+    P = int(ll.shape[1])
+    return P, (int(ll.stride(0)) if ll.shape[0] > 1 else P)
+
+
+def _device_vector(x, n: int, dev):
+    import torch
+
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
+    assert x.dtype == torch.float64 and x.shape == (n,) and x.stride(0) == 1
+    return x
+
+
+def mixture_loglik(pop: DevicePopulation, ll, w, out=None):
+    """``lpyl[s] = ln sum_p w[p] exp(ll[s, p])`` (``pmx_mixture_loglik_device``): the mixture log-likelihood of every
+    subject from the matrix ``loglik`` wrote; its sum is NPAG's objective.  Torch CUDA tensors on torch's current stream,
+    not synchronised.  Columns of weight 0 are skipped whatever they hold; a negative or NaN weight gives NaN."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    P, ld = _ll_matrix(pop, ll)
+    w = _device_vector(w, P, dev)
+    if out is None:
+        out = torch.empty((pop.n_subjects,), dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.shape == (pop.n_subjects,) and out.stride(0) == 1
+    _ffi.check(_ffi.lib().pmx_mixture_loglik_device(pop.handle, ll.data_ptr(), P, ld, w.data_ptr(), out.data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def d_function(pop: DevicePopulation, ll, log_pyl, out=None):
+    """``D[p] = sum_s exp(ll[s, p] - log_pyl[s]) - n_subjects`` (``pmx_dfunction_device``): the D-function of the candidate
+    support points whose columns ``ll`` holds; ``ParameterOptimizer.cost`` is ``-D``.  Torch CUDA tensors on torch's current
+    stream, not synchronised; the scratch slab is a torch allocation of this call.  D vectors of subject shards add."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    P, ld = _ll_matrix(pop, ll)
+    log_pyl = _device_vector(log_pyl, pop.n_subjects, dev)
+    if out is None:
+        out = torch.empty((P,), dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.shape == (P,) and out.stride(0) == 1
+    L = _ffi.lib()
+    scratch = torch.empty((max(int(L.pmx_dfunction_scratch_doubles(pop.n_subjects, P)), 1),), dtype=torch.float64, device=dev)
+    _ffi.check(L.pmx_dfunction_device(pop.handle, ll.data_ptr(), P, ld, log_pyl.data_ptr(), scratch.data_ptr(), out.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def last_kernel_name() -> str:
     return _ffi.lib().pmx_last_kernel_name().decode()
 
