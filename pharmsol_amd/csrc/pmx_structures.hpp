@@ -33,37 +33,15 @@
 
 namespace pmx {
 
-// exp() for the propagators' arguments (-lambda dt: finite, almost always <= 0).  Same scheme as the library's
-// (n = rint(x log2 e), r = x - n ln2 in two pieces, polynomial, scale by 2^n) without its special-case selects:
-// a degree-11 near-minimax polynomial on |r| <= ln2/2 (Chebyshev fit of e^r in 60-digit arithmetic, tools/exp_poly_fit.py:
-// approximation error 3.2e-18, i.e. the result is as good as the Horner evaluation in FMAs, within 1-2 ulp of the
-// library's; the degree-13 Taylor series this replaced was no more accurate and two FMAs longer); v_ldexp saturates to
-// 0 / inf by itself and NaN propagates.  ~17 VALU instructions instead of ~30.  (Keeping the constants resident in VGPRs
-// instead of literals was tried for the generic kernel: one wave of occupancy less, 6 % slower.)
-__device__ __forceinline__ double pmx_exp_poly(double x) {
-  const double n = __builtin_rint(x * 1.4426950408889634074);
-  double r = fma(n, -6.93147180369123816490e-01, x);  // ln2 high part: 21 trailing zero bits, n * hi is exact
-  r = fma(n, -1.90821492927058770002e-10, r);
-  double p = 2.5110180394444085e-08;
-  p = fma(p, r, 2.763282532538488e-07);
-  p = fma(p, r, 2.7557240532217283e-06);
-  p = fma(p, r, 2.480148497989361e-05);
-  p = fma(p, r, 0.00019841269890408497);
-  p = fma(p, r, 0.0013888888952784725);
-  p = fma(p, r, 0.008333333333319464);
-  p = fma(p, r, 0.04166666666648633);
-  p = fma(p, r, 0.1666666666666668);
-  p = fma(p, r, 0.5000000000000019);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(p, static_cast<int>(n));
-}
-
 // 2^t for the propagators: every exponential there is exp(-lambda dt), and lambda can carry the factor -log2(e) from the
 // once-per-lane (or once-per-rebuild) set-up, so the argument arrives in base 2: n = rint(t), r = t - n EXACTLY (no
-// two-piece ln2 reduction), degree-11 near-minimax polynomial of 2^r on |r| <= 1/2 (same fit: approximation error 3.2e-18,
-// 1.7e-16 worst relative error with the double coefficients), scale by 2^n.  15 FP64-rate instructions; the rounding of
-// t = lambda' dt is the same one ulp the product -lambda dt had.
+// two-piece ln2 reduction), degree-11 near-minimax polynomial of 2^r on |r| <= 1/2 (Chebyshev fit in 60-digit arithmetic,
+// tools/exp_poly_fit.py: approximation error 3.2e-18, 1.7e-16 worst relative error with the double coefficients), scale
+// by 2^n; v_ldexp saturates to 0 / inf by itself and NaN propagates.  15 FP64-rate instructions; the rounding of
+// t = lambda' dt is the same one ulp the product -lambda dt had.  (Keeping the constants resident in VGPRs instead of
+// literals was tried for the generic kernel: one wave of occupancy less, 6 % slower.)
+// (Tried: a 64-entry table of 2^(j/64) + a degree-5 polynomial, 11 FP64-rate instructions instead of 19.  The per-lane
+// table fetch cost more than the eight FMAs it replaced: jittered C3 1.99 -> 2.43 ms, C5 and the generic walker unchanged.)
 __device__ __forceinline__ double pmx_exp2(double t) {
   const double n = __builtin_rint(t);
   const double r = t - n;
@@ -103,10 +81,6 @@ __device__ __forceinline__ void pmx_exp2_n(const double (&t)[N], double (&e)[N])
   for (int k = 0; k < N; ++k) e[k] = ldexp(p[k], static_cast<int>(n[k]));
 }
 constexpr double kNegLog2e = -1.4426950408889634074;  // lambda' = -lambda log2(e):  exp(-lambda dt) = 2^(lambda' dt)
-
-// (Tried: a 64-entry table of 2^(j/64) + a degree-5 polynomial, 11 FP64-rate instructions instead of 19.  The per-lane
-// table fetch cost more than the eight FMAs it replaced: jittered C3 1.99 -> 2.43 ms, C5 and the generic walker unchanged.)
-__device__ __forceinline__ double pmx_exp(double x) { return pmx_exp_poly(x); }
 
 // 1/x to within an ulp or two: the hardware estimate polished by two Newton steps (what the IEEE division expands to,
 // minus its scaling and fix-up instructions: ~8 issue slots instead of ~15).  For the per-segment coefficient rebuild
@@ -455,18 +429,14 @@ struct ThreeCore {
     const double n = (2.0 * (a * a * a) - 9.0 * a * b + 27.0 * cc) * (1.0 / 27.0);
     const double q = (n * n) * 0.25 + (m * m * m) * (1.0 / 27.0);
     const bool ok = !(q > 0.0);  // reference panics on q > 0 (:32-34)
-    auto beta_of = [](double nn) { return -0.5 * nn; };
-    (void)beta_of;
     // The reference takes gamma = |beta + i alpha|, theta = atan2(alpha, beta), gamma^(1/3) and cos/sin(theta/3)
     // (:36-45), i.e. the principal cube root z = cr (cs + i sn) of w = beta + i alpha.  Three f64 transcendentals
-    // per segment dominate a covariate model's cost, so z is seeded in single precision and polished with two
-    // Newton steps z <- (2 z + w / z^2) / 3 in f64 (quadratic: 2e-6 -> 4e-12 -> rounding).  The seed needs no
+    // per segment dominate a covariate model's cost, so the angle is seeded in single precision.  The seed needs no
     // library call: gamma^2 = -m^3/27, so gamma^(1/3) = sqrt(-m/3); atan2 on alpha >= 0 is a degree-8 polynomial in
     // min/max (Abramowitz & Stegun 4.4.49, 2e-8) plus two reflections; theta/3 <= pi/3 goes straight to the hardware
     // sine/cosine.  Outside the float range the f64 functions are used directly.
     const double p3 = -m * (1.0 / 3.0);  // gamma^(2/3)
-#ifndef PMX_EIGEN_ZDOMAIN
-    // Real-root form (the default): with x = -lambda the reference's cubic is x^3 + a x^2 + b x + c, depressed by
+    // Real-root form: with x = -lambda the reference's cubic is x^3 + a x^2 + b x + c, depressed by
     // x = t - a/3 to t^3 + m t + n = 0, whose roots are t_k = 2 sqrt(p3) cos((theta - 2 pi k) / 3) - the same angle theta.
     // The trigonometric seed is taken in single precision (alpha = sqrt(-q) included: no f64 square root at all) and two
     // of the roots are polished by Newton steps on the depressed cubic itself, t <- t - f(t) / f'(t) with the quotient's
@@ -476,7 +446,7 @@ struct ThreeCore {
     // 80-bit evaluation over the C5 parameter ranges two steps reach 1e-15 / 5e-14 / 3e-12 relative (largest / middle /
     // smallest eigenvalue; the last is the cancellation in a/3 - t every formula shares), a third changes nothing.
     if (p3 > 1.0e-20 && p3 < 1.0e20) {
-      const float af = __builtin_amdgcn_sqrtf(static_cast<float>(-q)), bf = static_cast<float>(beta_of(n));
+      const float af = __builtin_amdgcn_sqrtf(static_cast<float>(-q)), bf = static_cast<float>(-0.5 * n);
       const float ax = fabsf(bf);
       const float mx = fmaxf(ax, af), mn = fminf(ax, af);
       const float t = mn * __builtin_amdgcn_rcpf(mx);
@@ -522,56 +492,14 @@ struct ThreeCore {
       l[2] = a3 - t2;
       return ok;
     }
-#endif
     const double alpha = sqrt(-q);
     const double beta = -0.5 * n;
-    double zr, zi;
-#ifdef PMX_EIGEN_ZDOMAIN
-    if (p3 > 1.0e-20 && p3 < 1.0e20) {
-      const float af = static_cast<float>(alpha), bf = static_cast<float>(beta);
-      const float ax = fabsf(bf);
-      const float mx = fmaxf(ax, af), mn = fminf(ax, af);
-      const float t = mn * __builtin_amdgcn_rcpf(mx);
-      const float s2 = t * t;
-      float pl = 0.0028662257f;
-      pl = fmaf(pl, s2, -0.0161657367f);
-      pl = fmaf(pl, s2, 0.0429096138f);
-      pl = fmaf(pl, s2, -0.0752896400f);
-      pl = fmaf(pl, s2, 0.1065626393f);
-      pl = fmaf(pl, s2, -0.1420889944f);
-      pl = fmaf(pl, s2, 0.1999355085f);
-      pl = fmaf(pl, s2, -0.3333314528f);
-      float thf = fmaf(pl * s2, t, t);
-      thf = (af > ax) ? (1.57079632679f - thf) : thf;
-      thf = (bf < 0.0f) ? (3.14159265359f - thf) : thf;
-      const float ph = thf * (1.0f / 3.0f);
-      const float crf = __builtin_amdgcn_sqrtf(static_cast<float>(p3));
-      zr = static_cast<double>(crf * __cosf(ph));
-      zi = static_cast<double>(crf * __sinf(ph));
-// (two steps: the seed is good to ~1e-6 and each step squares the relative error - 1e-12, then rounding level; a third
-// step bought nothing measurable, max rel err vs the oracle on C5 stays 1.5e-11, and cost 4 % of the kernel)
-#ifndef PMX_EIGEN_NEWTON
-#define PMX_EIGEN_NEWTON 2
-#endif
-#pragma unroll
-      for (int it = 0; it < PMX_EIGEN_NEWTON; ++it) {
-        const double z2r = zr * zr - zi * zi, z2i = 2.0 * zr * zi;
-        const double inv = pmx_rcp(z2r * z2r + z2i * z2i);
-        const double qr = (beta * z2r + alpha * z2i) * inv, qi = (alpha * z2r - beta * z2i) * inv;
-        zr = (2.0 * zr + qr) * (1.0 / 3.0);
-        zi = (2.0 * zi + qi) * (1.0 / 3.0);
-      }
-    } else
-#endif
-    {
-      const double gamma = sqrt(beta * beta + alpha * alpha);
-      const double theta = atan2(alpha, beta);
-      const double cr = cbrt(gamma);  // reference: gamma.powf(1.0/3.0)
-      double sn, cs;
-      sincos(theta / 3.0, &sn, &cs);
-      zr = cr * cs;
-      zi = cr * sn;
-    }
+    const double gamma = sqrt(beta * beta + alpha * alpha);
+    const double theta = atan2(alpha, beta);
+    const double cr = cbrt(gamma);  // reference: gamma.powf(1.0/3.0)
+    double sn, cs;
+    sincos(theta / 3.0, &sn, &cs);
+    const double zr = cr * cs, zi = cr * sn;
     const double rt3 = 1.7320508075688772;
     const double a3 = a * (1.0 / 3.0);
     l[0] = a3 + (zr + rt3 * zi);
@@ -640,9 +568,6 @@ __device__ __forceinline__ bool three_direct(double k10, double k12, double k13,
   const double K = k10 + k12 + k13;
   const double k1331 = k13 * k31, k1221 = k12 * k21, k1231 = k12 * k31, k2113 = k21 * k13;
   const double dts = dt * kNegLog2e;  // exp(-l dt) = 2^(l dts)
-#ifdef PMX_THREE_SEQ_EXP
-  if constexpr (ABS) ea = pmx_exp2(ka * dts);
-#else
   // the segment's exponentials as one interleaved batch (pmx_exp2_n), ahead of the coefficient loop
   double ev[3];
   if constexpr (ABS) {
@@ -657,7 +582,6 @@ __device__ __forceinline__ bool three_direct(double k10, double k12, double k13,
     const double t3[3] = {l[0] * dts, l[1] * dts, l[2] * dts};
     pmx_exp2_n<3>(t3, ev);
   }
-#endif
 #pragma unroll
   for (int k = 0; k < 9; ++k) p.m[k] = 0.0;
 #pragma unroll
@@ -665,20 +589,10 @@ __device__ __forceinline__ bool three_direct(double k10, double k12, double k13,
     p.j[k] = 0.0;
     g[k] = 0.0;
   }
-#ifdef PMX_THREE_ROLLED
-  double r0 = l[0], r1 = l[1], r2 = l[2];
-#pragma unroll 1
-  for (int i = 0; i < 3; ++i) {
-    const double li = r0, lo1 = r1, lo2 = r2;
-    r0 = lo1;
-    r1 = lo2;
-    r2 = li;
-#else
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const double li = l[i];
     const double lo1 = l[(i + 1) % 3], lo2 = l[(i + 2) % 3];
-#endif
     // the three reciprocals of this eigenvalue - 1/d_i, 1/l_i and (ABS) 1/(ka - l_i) - from ONE Newton reciprocal of
     // their product (a third of this loop's instructions were reciprocals)
     const double di = (lo1 - li) * (lo2 - li);
@@ -704,11 +618,7 @@ __device__ __forceinline__ bool three_direct(double k10, double k12, double k13,
     }
     const double u = k21 - li, v = k31 - li, w = K - li;
     const double ui = u * inv, vi = v * inv;
-#ifdef PMX_THREE_SEQ_EXP
-    const double e = pmx_exp2(li * dts);
-#else
     const double e = ev[i];
-#endif
     const double c0 = u * vi, c3 = k12 * vi, c6 = k13 * ui;
     p.m[0] = fma(c0, e, p.m[0]);
     p.m[1] = fma(k21 * vi, e, p.m[1]);
@@ -999,7 +909,7 @@ struct Structure<S_THREE_ABS> {
   }
 };
 
-// make_prop = the pmx_exp() calls + the coefficient combination
+// make_prop = the pmx_exp2() calls + the coefficient combination
 template <int ST>
 __device__ __forceinline__ void make_prop(const typename Structure<ST>::Coef& c, double dt, typename Structure<ST>::Prop& p) {
   double e[Structure<ST>::NE];
@@ -1008,9 +918,9 @@ __device__ __forceinline__ void make_prop(const typename Structure<ST>::Coef& c,
 }
 
 // The exponential ladder: when a step's length is n x the previous step's (n = 2, 3, 4; sampling designs on
-// 0.5/1/2/4/8/12/24 h grids are exactly that), pmx_exp(-lambda n dt) = pmx_exp(-lambda dt)^n costs n-1 multiplies instead of
-// an pmx_exp() call.  Each rung multiplies the relative error of the previous one by n; the host caps the
-// cumulative factor (pmx_plan.cpp ladder_code), which keeps the deviation from a fresh pmx_exp() below 1e-12.
+// 0.5/1/2/4/8/12/24 h grids are exactly that), exp(-lambda n dt) = exp(-lambda dt)^n costs n-1 multiplies instead of
+// a pmx_exp2() call.  Each rung multiplies the relative error of the previous one by n; the host caps the
+// cumulative factor (pmx_plan.cpp ladder_code), which keeps the deviation from a fresh pmx_exp2() below 1e-12.
 template <int NE>
 __device__ __forceinline__ void ladder_pow(double (&e)[NE], uint32_t n) {
 #pragma unroll
@@ -1023,12 +933,7 @@ __device__ __forceinline__ void ladder_pow(double (&e)[NE], uint32_t n) {
 
 // structures with the matrix-free rate-free step (direct0_make / direct0_apply)
 template <int ST>
-inline constexpr bool kHasDirect0 =
-#ifdef PMX_NO_DIRECT0
-    false;
-#else
-    (ST == S_THREE || ST == S_THREE_ABS);
-#endif
+inline constexpr bool kHasDirect0 = ST == S_THREE || ST == S_THREE_ABS;
 
 // covariate-derived rate constants: prepare + make for ONE segment.  Structures with a fused form provide
 // make_prop_dyn; the others go through their Coef.

@@ -1,6 +1,7 @@
-"""Coefficients of pmx_exp_poly / pmx_exp2 (pharmsol_amd/csrc/pmx_structures.hpp): Chebyshev fits (near-minimax) of
-e^r on |r| <= ln2/2 and 2^r on |r| <= 1/2 in 60-digit arithmetic, rounded to double, with the worst relative error of a
-double-precision Horner evaluation over 40001 points.  usage: python tools/exp_poly_fit.py [degree]"""
+"""Coefficients of pmx_exp2 (pharmsol_amd/csrc/pmx_structures.hpp): Chebyshev fits (near-minimax) of 2^r on |r| <= 1/2
+in 60-digit arithmetic, rounded to double, with the worst relative error of a double-precision Horner evaluation over
+40001 points.  The e^r fit on |r| <= ln2/2 is printed too, for the record: the base-e form it served is gone from the
+kernels, and the comparison of the two is why they use base 2.  usage: python tools/exp_poly_fit.py [degree]"""
 import sys
 
 import mpmath as mp
