@@ -893,7 +893,8 @@ static double dopri5_try(const ctx_t* c, const double* x, const double* p, const
 
 /* ---- PMX_SOLVER_ROS2: the stiff option (the role of the reference's OdeSolver::Bdf / Sdirk, ode/mod.rs:60-77); ROS2
  * (Verwer et al. 1999), same rule set as pmx_ode.hpp ros2_try: forward-difference Jacobian and time derivative,
- * elimination in the natural order, error estimate from the embedded first-order solution. ------------------------- */
+ * elimination in the natural order (built-in bodies) or with row exchanges (user bodies), error estimate from the
+ * embedded first-order solution. ---------------------------------------------------------------------------------- */
 static double ros2_try(const ctx_t* c, const double* x, const double* p, const double* rate, double t, double h,
                        double* xn) {
   const pmx_model_desc* m = c->m;
@@ -917,7 +918,21 @@ static double ros2_try(const ctx_t* c, const double* x, const double* p, const d
     double s = gh / dt;
     for (int i = 0; i < ns; i++) ft[i] = (f1[i] - f0[i]) * s;
   }
+  /* a user body: stage k exchanges rows k and i (their parts from column k on) when |W[i][k]| > |W[k][k]|, for
+   * i = k + 1 .. in turn; the right-hand sides replay the exchanges stage by stage (pmx_ode.hpp ros2_try) */
+  const int exchange = m->kernel == PMX_ODE_CUSTOM;
+  unsigned char swapped[PMX_MAX_STATES][PMX_MAX_STATES] = {{0}};
   for (int k = 0; k < ns; k++) {
+    for (int i = k + 1; exchange && i < ns; i++) {
+      if (fabs(W[i][k]) > fabs(W[k][k])) {
+        swapped[k][i] = 1;
+        for (int j = k; j < ns; j++) {
+          double up = W[k][j];
+          W[k][j] = W[i][j];
+          W[i][j] = up;
+        }
+      }
+    }
     double inv = 1.0 / W[k][k];
     for (int i = k + 1; i < ns; i++) {
       double l = W[i][k] * inv;
@@ -928,8 +943,15 @@ static double ros2_try(const ctx_t* c, const double* x, const double* p, const d
   }
 #define PMX_ROS2_SOLVE(b)                                          \
   do {                                                             \
-    for (int i = 1; i < ns; i++)                                   \
-      for (int j = 0; j < i; j++) (b)[i] -= W[i][j] * (b)[j];      \
+    for (int k = 0; k < ns; k++) {                                 \
+      for (int i = k + 1; i < ns; i++)                             \
+        if (swapped[k][i]) {                                       \
+          double up = (b)[k];                                      \
+          (b)[k] = (b)[i];                                         \
+          (b)[i] = up;                                             \
+        }                                                          \
+      for (int i = k + 1; i < ns; i++) (b)[i] -= W[i][k] * (b)[k]; \
+    }                                                              \
     for (int i = ns - 1; i >= 0; i--) {                            \
       for (int j = i + 1; j < ns; j++) (b)[i] -= W[i][j] * (b)[j]; \
       (b)[i] *= W[i][i];                                           \

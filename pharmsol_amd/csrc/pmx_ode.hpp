@@ -134,9 +134,18 @@ __device__ __forceinline__ double dopri5_try(const DevModel& m, const OdeLane<M>
 //     (I - gamma h J) k2 = f(t + h, y + h k1) - gamma h f_t - 2 k1
 //     y+ = y + 3/2 h k1 + 1/2 h k2,     error estimate = y+ - (y + h k1) = h/2 (k1 + k2)   (the embedded first-order solution)
 // One lane = one system of NS <= 8 states: J and f_t by forward differences (NS + 1 extra right-hand sides; exact up to
-// rounding for the linear compartmental bodies), the NS x NS factorisation fully unrolled in registers WITHOUT pivoting
-// (I - gamma h J of a compartmental system is a column-diagonally-dominant M-matrix, for which elimination in the natural
-// order is stable).  Same try/advance contract as DOPRI5, error exponent -1/2.
+// rounding for the linear compartmental bodies), the NS x NS factorisation fully unrolled in registers.
+//   built-in bodies: WITHOUT pivoting.  I - gamma h J of a compartmental system is a column-diagonally-dominant M-matrix,
+//     for which elimination in the natural order is stable.
+//   user bodies (M::CUSTOM): with partial pivoting.  Growth, positive feedback or a predator-prey term let a diagonal
+//     entry of W shrink to nothing while W stays well conditioned; the natural order then loses digits silently (the
+//     error estimate does not see it: tests/golden/gen_ode_exact_general.py, the pivot ladder).  Stage k compares
+//     |W[i][k]| with |W[k][k]| for i = k + 1 .. and exchanges the two rows' remaining parts by compare-and-select on the
+//     unrolled registers when the lower one is strictly larger - no indexed rows, which would send W to scratch.  The
+//     right-hand sides replay the exchanges stage by stage from one bit mask (LINPACK's dgefa / dgesl arrangement:
+//     multipliers stay where their stage put them).  An M-matrix never exchanges, and a stage at which no lane of the wave
+//     does is skipped by a wave-uniform branch (profiles/ros2_pivot.txt).
+// Same try/advance contract as DOPRI5, error exponent -1/2.
 // JNORM (SOLV_AUTO only): also hands back *aux = ||J||_inf, the largest absolute row sum of the difference Jacobian
 // before its scaling by -gamma h.
 template <class M, bool JNORM = false>
@@ -182,9 +191,31 @@ __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& 
 #pragma unroll
     for (int i = 0; i < NS; ++i) ft[i] = (f1[i] - f0[i]) * s;
   }
-  // W = L U in place (unit lower triangle below the diagonal), natural order
+  // W = L U in place (unit lower triangle below the diagonal); natural order for the built-in bodies, row exchanges
+  // for a user body: bit (k, i) of `swaps` = stage k exchanged rows k and i, in the order the exchanges were made
+  static_assert(NS * (NS - 1) / 2 <= 32, "one bit per (stage, row) pair");
+  [[maybe_unused]] uint32_t swaps = 0;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
+    if constexpr (M::CUSTOM) {
+      bool larger = false;  // some entry below the diagonal is: without one no exchange below happens
+#pragma unroll
+      for (int i = k + 1; i < NS; ++i) larger |= fabs(W[i][k]) > fabs(W[k][k]);  // (false for NaN)
+      if (__any(larger ? 1 : 0)) {  // wave-uniform: a wave of M-matrices walks past all of this
+        int bit = k * (2 * NS - k - 1) / 2;
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i, ++bit) {
+          const bool sw = fabs(W[i][k]) > fabs(W[k][k]);
+          swaps |= sw ? (1u << bit) : 0u;
+#pragma unroll
+          for (int j = k; j < NS; ++j) {  // (the multipliers left of column k stay where stage j < k put them)
+            const double up = W[k][j], low = W[i][j];
+            W[k][j] = sw ? low : up;
+            W[i][j] = sw ? up : low;
+          }
+        }
+      }
+    }
     const double inv = 1.0 / W[k][k];
 #pragma unroll
     for (int i = k + 1; i < NS; ++i) {
@@ -195,11 +226,31 @@ __device__ __forceinline__ double ros2_try(const DevModel& m, const OdeLane<M>& 
     }
     W[k][k] = inv;  // (the diagonal keeps its reciprocal for the back substitutions)
   }
-  auto solve = [&W](double (&b)[NS]) {
+  auto solve = [&W, swaps](double (&b)[NS]) {
+    if constexpr (M::CUSTOM) {  // stage by stage: the stage's exchanges, then its column of multipliers
+      const bool replay = __any(swaps != 0u ? 1 : 0) != 0;  // (wave-uniform)
+      int at = 0;
 #pragma unroll
-    for (int i = 1; i < NS; ++i) {
+      for (int k = 0; k < NS; ++k) {
+        if (replay) {
 #pragma unroll
-      for (int j = 0; j < i; ++j) b[i] -= W[i][j] * b[j];
+          for (int i = k + 1; i < NS; ++i) {
+            const bool sw = ((swaps >> (at + i - k - 1)) & 1u) != 0u;
+            const double up = b[k], low = b[i];
+            b[k] = sw ? low : up;
+            b[i] = sw ? up : low;
+          }
+        }
+        at += NS - 1 - k;
+#pragma unroll
+        for (int i = k + 1; i < NS; ++i) b[i] -= W[i][k] * b[k];
+      }
+    } else {
+#pragma unroll
+      for (int i = 1; i < NS; ++i) {
+#pragma unroll
+        for (int j = 0; j < i; ++j) b[i] -= W[i][j] * b[j];
+      }
     }
 #pragma unroll
     for (int i = NS - 1; i >= 0; --i) {

@@ -25,7 +25,10 @@ Stored per case: `ros2`, `exact` (the true solution), `n_steps`, `max_step_err`,
     a first-order bound on accumulated rounding.  A step is one solve with W and a handful of sums; elimination in the
     natural order on a column-diagonally-dominant M-matrix has no growth, so a step perturbs by O(u) cond_1(W) |x| with
     cond_1(W) <= ||W||_1 ||W^-1||_1 <= 1 + gamma h ||J||_1, plus the four sums of the stage formulas; later steps are
-    contractive (|R(z)| <= 1 at every eigenvalue and step length, asserted).
+    contractive (|R(z)| <= 1 at every eigenvalue and step length, asserted).  The bound is valid for THIS file's bodies:
+    each is a compartmental M-matrix, Michaelis-Menten or the one-state non-autonomous body, none with growth.  A body
+    with a growing state, feedback or a predator-prey term obeys neither ||W^-1||_1 <= 1 nor the contraction, and the
+    natural order is not stable for it: gen_ode_exact_general.py measures cond_1(W) and the amplification per step there.
   diff_noise: what rounding in the difference quotients costs, which no double-precision implementation avoids: two more
     exact walks with every J entry shifted by +/- 4u max(|f0_i|, |f1_i|) / d_j and f_t likewise (an entry whose two
     function values are equal stays: that difference is exact in any arithmetic); the larger deviation.
