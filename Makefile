@@ -8,7 +8,7 @@ LIB := pharmsol_amd/lib/libpmx_hip.so
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
 # the kernel units: one translation unit per kernel family (pmx_lanes.hpp lists them)
-KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util pmx_mixture
+KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util pmx_mixture pmx_posterior
 OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_model.o $(CSRC)/build/pmx_host.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_source.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 

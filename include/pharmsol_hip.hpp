@@ -440,6 +440,16 @@ class Equation {
     void predict_matrix(const double* theta, int64_t n_support, double* pred, uint8_t* status, bool throw_on_pair_failure = false) {
       check(pmx_predict(eq_.handle(), pop_, theta, n_support, pred, n_support, status), !throw_on_pair_failure);
     }
+    /// population predictions: mean / median [n_observations] of every row of the prediction matrix, weighted by w (either may be null)
+    void population_predictions(const double* theta, int64_t n_support, const double* w, double* mean, double* median,
+                                uint8_t* status, bool throw_on_pair_failure = false) {
+      check(pmx_summarize_predictions(eq_.handle(), pop_, nullptr, theta, n_support, w, mean, median, status), !throw_on_pair_failure);
+    }
+    /// individual predictions: the same, weighted by the posterior of the subject that owns the row
+    void posterior_predictions(const double* theta, int64_t n_support, const double* w, const std::vector<pmx_error_model>& error_models,
+                               double* mean, double* median, uint8_t* status, bool throw_on_pair_failure = false) {
+      check(pmx_summarize_predictions(eq_.handle(), pop_, error_models.data(), theta, n_support, w, mean, median, status), !throw_on_pair_failure);
+    }
     const pmx_population* handle() const { return pop_; }
 
    private:

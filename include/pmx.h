@@ -620,6 +620,46 @@ int32_t pmx_mixture_loglik(const pmx_model* model, const pmx_population* pop, co
 int32_t pmx_dfunction(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em, const double* theta,
                       int64_t n_cand, const double* lpyl, double* D, uint8_t* status /*[n_subjects x n_cand] or NULL*/);
 
+/* What a fit reports of the matrix pmx_predict writes, computed where the matrix is: per observation row, the weighted
+ * mean and the weighted median of pred[row][.] over the support points - weighted by the support-point weights w
+ * (population prediction) or by the posterior of the subject s(row) that owns the row (individual prediction) - and the
+ * posterior itself, where Bayesian dose individualisation starts.
+ *   q[s][p]     = w[p] exp(ll[s][p] - lpyl[s]) where w[p] > 0, else exactly 0; lpyl from pmx_mixture_loglik.  The
+ *                 difference is formed in the log domain: w exp(ll) / sum underflows to 0 / 0 for a subject with some 70
+ *                 observations.  Population mode: q[p] = w[p] for every row.
+ *   mean[row]   = sum_p q pred[row][p] / sum_p q over the columns with q > 0; dividing by the accumulated sum, so that an
+ *                 unnormalised w and the rounding of lpyl cancel.
+ *   median[row] = the LOWER WEIGHTED MEDIAN: the smallest v = pred[row][p] among the columns with q > 0 such that
+ *                 sum_{p': q > 0, pred[row][p'] <= v} q >= (sum_p q) / 2.  It is one of the row's own values, bit for bit
+ *                 (of values that compare equal - duplicates, -0.0 and +0.0 - any one).  The reference has no such
+ *                 function; PMcore's weighted median is the same definition.
+ * Edges.  A column with w[p] == 0 is skipped whatever ll and pred hold there; ll = -inf gives q = 0; a negative or NaN
+ * weight gives NaN everywhere (device forms) or is refused (host form); a NaN q - a failed pair under positive weight -
+ * gives NaN in every row of that subject and in no other subject's; a NaN prediction under q > 0 gives a NaN mean and a
+ * NaN median in that row only; a row whose q are all 0 gives NaN for both; +-inf predictions follow IEEE (the mean may be
+ * +-inf or NaN, the median orders them).
+ * Everything is summed in a fixed order: a result is bit-identical from run to run, for any alignment and any ld.
+ * Sharding by subjects needs nothing more: the shards' rows concatenate.
+ *
+ * Device forms: stream-ordered, not synchronised; 8-byte alignment is all any pointer needs.  d_post: [n_subjects] rows
+ * ld_post >= n_support doubles apart, columns [n_support, ld_post) are never written.  d_ll == NULL (then d_lpyl must be
+ * NULL too, and ld_ll is ignored): population mode.  At least one of d_mean, d_median; each [n_observations]. */
+int32_t pmx_posterior_device(const pmx_population* pop, const double* d_ll, int64_t n_support, int64_t ld_ll,
+                             const double* d_w /*[n_support]*/, const double* d_lpyl /*[n_subjects]*/, double* d_post,
+                             int64_t ld_post, void* stream);
+int32_t pmx_summarize_predictions_device(const pmx_population* pop, const double* d_pred, int64_t n_support, int64_t ld_pred,
+                                         const double* d_w /*[n_support]*/, const double* d_ll /*or NULL*/, int64_t ld_ll,
+                                         const double* d_lpyl /*NULL iff d_ll is*/, double* d_mean /*or NULL*/,
+                                         double* d_median /*or NULL*/, void* stream);
+/* Host form: theta in, n_observations doubles out per requested output; neither matrix crosses the link.  em == NULL:
+ * population mode; otherwise predict, loglik and the mixture rows run first.  Errors and status as for
+ * pmx_mixture_loglik: w is checked before any work, and with failed pairs the call returns PMX_ERR_PAIR_FAILED, the status
+ * array (if given) is filled and the outputs are still copied out - NaN in the rows of a subject for which a failed
+ * support point carries weight, clean where its weight is 0. */
+int32_t pmx_summarize_predictions(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em /*or NULL*/,
+                                  const double* theta, int64_t n_support, const double* w, double* mean /*or NULL*/,
+                                  double* median /*or NULL*/, uint8_t* status /*[n_subjects x n_support] or NULL*/);
+
 /* Row pitch (ld_pred, in doubles) at which the prediction kernels write fastest: n_support rounded up to a multiple of 16,
  * so every row starts on a 128-byte boundary.  Measured on C3 (profiles/r03/ld_by_allocation.txt): 1000 -> 1008 doubles
  * gives 6.45 -> 6.8 TB/s in fast allocations and 5.3 -> 5.5 in slow ones; a pitch that is a multiple of 8 but not 16

@@ -284,6 +284,35 @@ int32_t pmx_dfunction_device(const pmx_population* cpop, const double* d_ll, int
   return PMX_OK;
 }
 
+// the posterior, and the summaries of a matrix pmx_predict_device wrote (pmx_posterior.hip)
+int32_t pmx_posterior_device(const pmx_population* cpop, const double* d_ll, int64_t n_support, int64_t ld_ll,
+                             const double* d_w, const double* d_lpyl, double* d_post, int64_t ld_post, void* stream) {
+  DeviceCall c;
+  const int32_t rc = c.begin(cpop, {{cpop && d_ll && d_w && d_lpyl && d_post, kNull},
+                                    {matrix_ok(n_support, ld_ll), "n_support must be > 0 and ld_ll >= n_support"},
+                                    {ld_post >= n_support, "ld_post must be >= n_support"}});
+  if (rc != PMX_OK) return rc;
+  PMX_HIP(pmx::launch_posterior_rows(d_ll, c.pop->hp.n_subjects, n_support, ld_ll, d_w, d_lpyl, d_post, ld_post, stream));
+  return PMX_OK;
+}
+
+int32_t pmx_summarize_predictions_device(const pmx_population* cpop, const double* d_pred, int64_t n_support, int64_t ld_pred,
+                                         const double* d_w, const double* d_ll, int64_t ld_ll, const double* d_lpyl,
+                                         double* d_mean, double* d_median, void* stream) {
+  DeviceCall c;
+  int32_t rc = c.begin(cpop, {{cpop && d_pred && d_w, kNull},
+                              {d_mean || d_median, "d_mean and d_median are both null: nothing to compute"},
+                              {(d_ll == nullptr) == (d_lpyl == nullptr), "d_ll and d_lpyl go together: both (posterior) or neither (population)"},
+                              {matrix_ok(n_support, ld_pred), "n_support must be > 0 and ld_pred >= n_support"},
+                              {!d_ll || ld_ll >= n_support, "ld_ll must be >= n_support"}});
+  if (rc != PMX_OK) return rc;
+  if (d_ll && (rc = resident_obs_off(c.pop)) != PMX_OK) return rc;
+  const pmx::SummaryArgs a{d_pred, c.pop->hp.n_obs, n_support, ld_pred, d_w, d_ll, ld_ll, d_lpyl, c.pop->d_subj_obs_off,
+                           c.pop->hp.n_subjects, c.pop->max_subject_rows, d_mean, d_median};
+  PMX_HIP(pmx::launch_summary_rows(a, stream));
+  return PMX_OK;
+}
+
 int32_t pmx_time_predict_device(const pmx_model* model, const pmx_population* cpop, const double* d_theta,
                                 int64_t n_support, double* d_pred, int64_t ld_pred, int32_t reps, void* stream,
                                 double* ms_per_pass) {

@@ -1,5 +1,5 @@
 // pmx_host.cpp — the HOST-pointer entry points of include/pmx.h: pmx_predict, pmx_predict_batch, pmx_loglik,
-// pmx_loglik_batch, pmx_mixture_loglik, pmx_dfunction.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
+// pmx_loglik_batch, pmx_mixture_loglik, pmx_dfunction, pmx_summarize_predictions.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
 // result out.
 #include <cstring>
 #include <limits>
@@ -234,14 +234,24 @@ int32_t predict_host(const pmx_model* model, const pmx_population* cpop, const d
 // The log-likelihood part every host form shares: begin, the kernels, and the invalid-sigma counter read back.  On
 // PMX_OK call.d_out() holds ll[s][p] (matrix shape, dense) or ll[s] (batch shape: subject s with theta row s,
 // likelihood/mod.rs:119-177) on the device, ordered on call.ws->compute.
+int32_t loglik_into(HostCall& call, const pmx_model* model, pmx_population* pop, const pmx_error_model* em, int64_t P,
+                    int batch, double* d_ll);
 int32_t loglik_on_device(HostCall& call, const pmx_model* model, pmx_population* pop, const pmx_error_model* em,
                          const double* theta, int64_t P, int batch) {
-  int32_t rc = call.begin(model, pop, theta, P, batch, pop->hp.n_subjects);
-  if (rc != PMX_OK) return rc;
+  const int32_t rc = call.begin(model, pop, theta, P, batch, pop->hp.n_subjects);
+  return rc != PMX_OK ? rc : loglik_into(call, model, pop, em, P, batch, call.d_out());
+}
+
+// ... after begin(): the kernels write the dense d_ll (rows call.Pd apart) from the theta and into the status begin() set up
+int32_t loglik_into(HostCall& call, const pmx_model* model, pmx_population* pop, const pmx_error_model* em, int64_t P,
+                    int batch, double* d_ll) {
+  int32_t rc;
   HostWorkspace* ws = call.ws;
   const int32_t* d_sigma_err = nullptr;
-  LLRequest req{em, call.d_out(), call.Pd, &d_sigma_err};
-  if ((rc = call.run(model, pop, P, batch, &req)) != PMX_OK) return rc;
+  LLRequest req{em, d_ll, call.Pd, &d_sigma_err};
+  if ((rc = enqueue(model, pop, static_cast<const double*>(ws->d_theta), P, batch, d_ll, call.Pd,
+                    static_cast<uint8_t*>(ws->d_status), ws->compute, &req)) != PMX_OK)
+    return rc;
   if (d_sigma_err) {  // ErrorModelError::NegativeSigma / NonFiniteSigma (error_model.rs:1073-1077), found on the device
     PMX_HIP(hipMemcpyAsync(ws->h_flag, d_sigma_err, sizeof(int32_t), hipMemcpyDeviceToHost, ws->compute));
     PMX_HIP(hipStreamSynchronize(ws->compute));
@@ -300,6 +310,16 @@ int32_t reduce_host(const pmx_model* model, const pmx_population* cpop, const pm
   return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
 }
 
+// weights arrive on the host: a negative or NaN entry, or no positive one, is refused before any work
+int32_t check_weights(const double* w, int64_t n) {
+  bool any_positive = false;
+  for (int64_t p = 0; p < n; ++p) {
+    if (!(w[p] >= 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "w[" + std::to_string(p) + "] is negative or NaN");
+    any_positive = any_positive || w[p] > 0.0;
+  }
+  return any_positive ? PMX_OK : fail(PMX_ERR_INVALID_ARGUMENT, "w holds no positive entry");
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,12 +346,8 @@ int32_t pmx_mixture_loglik(const pmx_model* model, const pmx_population* pop, co
   pmx::clear_error();
   if (!model || !pop || !em || !theta || !w || !lpyl) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
   if (n_support <= 0) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0");
-  bool any_positive = false;
-  for (int64_t p = 0; p < n_support; ++p) {
-    if (!(w[p] >= 0.0)) return fail(PMX_ERR_INVALID_ARGUMENT, "w[" + std::to_string(p) + "] is negative or NaN");
-    any_positive = any_positive || w[p] > 0.0;
-  }
-  if (!any_positive) return fail(PMX_ERR_INVALID_ARGUMENT, "w holds no positive entry");
+  const int32_t rc = check_weights(w, n_support);
+  if (rc != PMX_OK) return rc;
   const int64_t S = pop->hp.n_subjects;
   return reduce_host(model, pop, em, theta, n_support, w, n_support, lpyl, S, 0, status,
                      [&](const double* d_ll, const double* d_w, double* d_lpyl, double*, hipStream_t st) {
@@ -350,6 +366,48 @@ int32_t pmx_dfunction(const pmx_model* model, const pmx_population* pop, const p
                      [&](const double* d_ll, const double* d_lpyl, double* d_D, double* d_scratch, hipStream_t st) {
                        return pmx::launch_dfunction(d_ll, S, n_cand, n_cand, d_lpyl, d_scratch, d_D, st);
                      });
+}
+
+// predict, then - posterior mode - loglik and the mixture rows, then the summaries (pmx_posterior.hip), all on the
+// private stream: pred stays in the workspace's output matrix, ll and the small vectors in its reduction buffer
+// [w | lpyl | mean | median | ll], and n_observations doubles come back per requested output.
+int32_t pmx_summarize_predictions(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em,
+                                  const double* theta, int64_t n_support, const double* w, double* mean, double* median,
+                                  uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !cpop || !theta || !w) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!mean && !median) return fail(PMX_ERR_INVALID_ARGUMENT, "mean and median are both null: nothing to compute");
+  if (n_support <= 0) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0");
+  int32_t rc = check_weights(w, n_support);
+  if (rc != PMX_OK) return rc;
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  const int64_t S = pop->hp.n_subjects, n_obs = pop->hp.n_obs, P = n_support;
+  HostCall call;
+  if ((rc = call.begin(model, pop, theta, P, 0, n_obs)) != PMX_OK) return rc;
+  if ((rc = call.run(model, pop, P, 0)) != PMX_OK) return rc;
+  HostWorkspace* ws = call.ws;
+  const size_t n_red = static_cast<size_t>(P + S + 2 * n_obs + (em ? S * P : 0));
+  if ((rc = ws_reserve(&ws->d_red, &ws->red_cap, n_red * sizeof(double))) != PMX_OK) return rc;
+  double* d_w = static_cast<double*>(ws->d_red);
+  double* d_lpyl = d_w + P;
+  double* d_mean = d_lpyl + S;
+  double* d_median = d_mean + n_obs;
+  double* d_ll = d_median + n_obs;
+  PMX_HIP(hipMemcpyAsync(d_w, w, static_cast<size_t>(P) * sizeof(double), hipMemcpyHostToDevice, ws->compute));
+  if (em) {
+    if ((rc = loglik_into(call, model, pop, em, P, 0, d_ll)) != PMX_OK) return rc;
+    PMX_HIP(pmx::launch_mixture_rows(d_ll, S, P, P, d_w, d_lpyl, ws->compute));
+    if ((rc = resident_obs_off(pop)) != PMX_OK) return rc;
+  }
+  const pmx::SummaryArgs a{call.d_out(), n_obs, P, P, d_w, em ? d_ll : nullptr, P, em ? d_lpyl : nullptr, pop->d_subj_obs_off,
+                           S, pop->max_subject_rows, mean ? d_mean : nullptr, median ? d_median : nullptr};
+  PMX_HIP(pmx::launch_summary_rows(a, ws->compute));
+  bool any_failed = false;
+  if ((rc = ws_finish_status(ws, status, call.n_status, &any_failed)) != PMX_OK) return rc;
+  const size_t out_bytes = static_cast<size_t>(n_obs) * sizeof(double);
+  if (mean && (rc = ws_copy_out(ws, mean, out_bytes, d_mean, out_bytes, 1)) != PMX_OK) return rc;
+  if (median && (rc = ws_copy_out(ws, median, out_bytes, d_median, out_bytes, 1)) != PMX_OK) return rc;
+  return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
 }
 
 }  // extern "C"

@@ -157,6 +157,10 @@ struct pmx_population {
   uint32_t valued_outeq_mask = 0;  // bit q: some observation on output q carries a value
   bool any_censored = false;
   std::vector<void*> ll_allocs;
+  // the rows of each subject, for the summaries of a prediction matrix (pmx_posterior.hip): uploaded at the first such
+  // call (resident_obs_off), freed with ll_allocs
+  const int64_t* d_subj_obs_off = nullptr;
+  int64_t max_subject_rows = 0;
   std::vector<std::unique_ptr<DeviceStream>> streams;  // one per model flavour, built lazily
   pmx_population();
   ~pmx_population();  // (pmx_host.cpp, where HostWorkspace is complete; pmx_population_destroy too)
@@ -195,6 +199,8 @@ int32_t get_stream(pmx_population* pop, const pmx::CompileKey& key, const pmx::C
 int32_t acquire_ll_slot(const pmx_model* model, pmx_population* pop, DeviceStream* ds, const pmx_error_model* em,
                         void* stream, DeviceStream::LLCache** out, bool batch);
 void release_ll_slot(pmx_population* pop, DeviceStream::LLCache* slot, void* stream);
+// pop->d_subj_obs_off / max_subject_rows, uploaded once per population (the population's device is current)
+int32_t resident_obs_off(pmx_population* pop);
 
 // ---- pmx_launch.cpp
 // What the model contributes to the op stream, under this snapshot of the switches, on a population with / without

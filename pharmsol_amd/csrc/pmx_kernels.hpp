@@ -169,6 +169,30 @@ inline int64_t dfunction_tiles(int64_t S, int64_t n_cand) {
 hipError_t launch_dfunction(const double* d_ll, int64_t S, int64_t n_cand, int64_t ld, const double* d_lpyl,
                             double* d_scratch, double* d_D, void* stream);
 
+// The summaries of a prediction matrix pred[n_obs][ld_pred] over its support points (pmx_posterior.hip).
+//   q[s][p] = w[p] exp(ll[s][p] - lpyl[s]) where w[p] > 0, else 0: a wave owns a row of ll, the columns [P, ld_post) of
+//   d_post are never written
+hipError_t launch_posterior_rows(const double* d_ll, int64_t S, int64_t P, int64_t ld_ll, const double* d_w,
+                                 const double* d_lpyl, double* d_post, int64_t ld_post, void* stream);
+//   mean[row] = sum_p q pred[row][p] / sum_p q and the lower weighted median of pred[row][.], q the row's subject's
+//   posterior (ll, lpyl given) or w itself (both null).  A work item is up to rows_per_item consecutive rows - of one
+//   subject in posterior mode - and is owned by a wave up to kSummaryWaveMax columns, by a block of four beyond; the
+//   item's q and the row in hand stay in registers up to kSummaryRegisterMax columns, wider rows are re-read.
+constexpr int64_t kSummaryWaveMax = 1024, kSummaryRegisterMax = 4096, kSummaryRowsPerItem = 16;
+struct SummaryArgs {
+  const double* pred;
+  int64_t n_obs, P, ld_pred;
+  const double* w;
+  const double* ll;  // null: population mode
+  int64_t ld_ll;
+  const double* lpyl;
+  const int64_t* subj_obs_off;  // [S + 1], on the device (posterior mode)
+  int64_t S, max_subject_rows;
+  double* mean;    // [n_obs] or null
+  double* median;  // [n_obs] or null
+};
+hipError_t launch_summary_rows(const SummaryArgs& a, void* stream);
+
 // One entry per kernel family, at the end of the family's translation unit (pmx_grid.hip, pmx_classed.hip, ...): it
 // switches on the model's kernel id and the route's variant flags and enqueues that instantiation.  Policy-free: which
 // family, which variant and which geometry is the route's (pmx_launch.cpp plan_routes).

@@ -7,6 +7,7 @@
 //   pmx_ode_builtin.hip                                          built-in ODE bodies (walkers and steppers: pmx_ode.hpp)
 //   pmx_util.hip                                                 log-likelihood tables, status scan, streaming fill
 //   pmx_mixture.hip                                              reductions of the log-likelihood matrix: mixture rows, D-function
+//   pmx_posterior.hip                                            posterior rows; weighted mean and median of the prediction rows
 //
 // One wavefront lane per (subject, support point) pair, two lane mappings:
 //

@@ -220,6 +220,17 @@ int32_t acquire_ll_slot(const pmx_model* model, pmx_population* pop, DeviceStrea
   return PMX_OK;
 }
 
+int32_t resident_obs_off(pmx_population* pop) {
+  std::lock_guard<std::mutex> lock(pop->mu);
+  if (pop->d_subj_obs_off != nullptr) return PMX_OK;
+  const auto& off = pop->hp.subj_obs_off;
+  int64_t most = 0;
+  for (size_t s = 0; s + 1 < off.size(); ++s) most = off[s + 1] - off[s] > most ? off[s + 1] - off[s] : most;
+  const int32_t rc = upload(off, &pop->d_subj_obs_off, &pop->ll_allocs);
+  if (rc == PMX_OK) pop->max_subject_rows = most;
+  return rc;
+}
+
 void release_ll_slot(pmx_population* pop, DeviceStream::LLCache* slot, void* stream) {
   std::lock_guard<std::mutex> lock(pop->mu);
   (void)hipEventRecord(slot->ev, static_cast<hipStream_t>(stream));

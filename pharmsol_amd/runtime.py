@@ -452,6 +452,58 @@ def d_function(pop: DevicePopulation, ll, log_pyl, out=None):
     return out
 
 
+def posterior(pop: DevicePopulation, ll, w, log_pyl, out=None):
+    """``q[s, p] = w[p] exp(ll[s, p] - log_pyl[s])`` where ``w[p] > 0``, else 0 (``pmx_posterior_device``): every
+    subject's posterior over the support points, from the matrix ``loglik`` wrote and ``mixture_loglik``'s output; a
+    ``[S, P]`` tensor.  Torch CUDA tensors on torch's current stream, not synchronised.  A negative or NaN weight gives
+    NaN everywhere."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    P, ld = _ll_matrix(pop, ll)
+    w = _device_vector(w, P, dev)
+    log_pyl = _device_vector(log_pyl, pop.n_subjects, dev)
+    if out is None:
+        out = torch.empty((pop.n_subjects, P), dtype=torch.float64, device=dev)
+    assert out.shape == (pop.n_subjects, P)
+    _, ld_out = _ll_matrix(pop, out)
+    _ffi.check(_ffi.lib().pmx_posterior_device(pop.handle, ll.data_ptr(), P, ld, w.data_ptr(), log_pyl.data_ptr(),
+                                               out.data_ptr(), ld_out, torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def summarize_predictions(pop: DevicePopulation, pred, w, ll=None, log_pyl=None, mean: bool = True, median: bool = True):
+    """``(mean, median)`` of every row of ``pred[n_observations, P]`` over the support points
+    (``pmx_summarize_predictions_device``), weighted by ``w`` (population predictions) or - ``ll`` and ``log_pyl`` given -
+    by the posterior of the subject that owns the row (individual predictions); the median is the lower weighted median
+    and one of the row's own values.  CUDA tensors of length ``n_observations`` on torch's current stream, not
+    synchronised; ``None`` for an output that was not requested."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    assert pred.is_cuda and pred.dtype == torch.float64 and pred.dim() == 2 and pred.stride(1) == 1
+    assert pred.shape[0] == pop.n_observations
+    P = int(pred.shape[1])
+    ld_pred = int(pred.stride(0)) if pred.shape[0] > 1 else P
+    w = _device_vector(w, P, dev)
+    if (ll is None) != (log_pyl is None):
+        raise ValueError("ll and log_pyl go together: both (posterior) or neither (population)")
+    if not (mean or median):
+        raise ValueError("neither mean nor median requested")
+    ld_ll = 0
+    if ll is not None:
+        P_ll, ld_ll = _ll_matrix(pop, ll)
+        assert P_ll == P
+        log_pyl = _device_vector(log_pyl, pop.n_subjects, dev)
+    out_mean = torch.empty((pop.n_observations,), dtype=torch.float64, device=dev) if mean else None
+    out_median = torch.empty((pop.n_observations,), dtype=torch.float64, device=dev) if median else None
+    _ffi.check(_ffi.lib().pmx_summarize_predictions_device(
+        pop.handle, pred.data_ptr(), P, ld_pred, w.data_ptr(), ll.data_ptr() if ll is not None else None, ld_ll,
+        log_pyl.data_ptr() if ll is not None else None, out_mean.data_ptr() if mean else None,
+        out_median.data_ptr() if median else None, torch.cuda.current_stream(dev).cuda_stream))
+    return out_mean, out_median
+
+
 def last_kernel_name() -> str:
     return _ffi.lib().pmx_last_kernel_name().decode()
 
