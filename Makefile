@@ -72,7 +72,12 @@ oracle:
 clean:
 	rm -rf $(CSRC)/build pharmsol_amd/lib oracle/_build
 
-.PHONY: all oracle clean asm plan_fingerprint plan_fingerprint_san jit_source_fingerprint jit_source_fingerprint_san
+# the two generated bindings of include/pmx.h (tools/pmx_header.py reads the header for both); run after changing the header
+bindings:
+	python3 tools/gen_rust_binding.py
+	python3 tools/gen_python_binding.py
+
+.PHONY: all oracle clean asm bindings plan_fingerprint plan_fingerprint_san jit_source_fingerprint jit_source_fingerprint_san
 
 # Fingerprint of every array the population compiler produces (tests/test_plan_fingerprint.py compares its output with
 # tests/golden/plan_fingerprints.txt).  Host sources only.  FPBIN: where the program goes.  plan_fingerprint_san: the same

@@ -15,94 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMX_LIB") or os.path.join(_HERE, "lib", "libpmx_hip.so")
 _lib = None
 
-# every symbol include/pmx.h declares: (name, restype, argtypes)
-_PD = C.POINTER(_abi.pmx_population_desc)
-_MD = C.POINTER(_abi.pmx_model_desc)
-SYMBOLS = [
-    ("pmx_abi_version", C.c_int32, []),
-    ("pmx_sizeof_model_desc", C.c_int64, []),
-    ("pmx_sizeof_population_desc", C.c_int64, []),
-    ("pmx_sizeof_struct", C.c_int64, [C.c_char_p]),
-    ("pmx_device_count", C.c_int32, []),
-    ("pmx_population_create", C.c_int32, [_PD, C.c_int32, C.POINTER(C.c_void_p)]),
-    ("pmx_population_create_shard", C.c_int32, [_PD, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
-    ("pmx_shard_bounds", C.c_int32, [_PD, C.c_int32, C.c_void_p]),
-    ("pmx_shard_rows", C.c_int32, [_PD, C.c_int32, C.c_void_p, C.c_void_p]),
-    ("pmx_comm_unique_id", C.c_int32, [C.c_void_p]),
-    ("pmx_comm_create", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    ("pmx_comm_destroy", None, [C.c_void_p]),
-    ("pmx_comm_size", C.c_int32, [C.c_void_p]),
-    ("pmx_comm_rank", C.c_int32, [C.c_void_p]),
-    ("pmx_allgather_predictions", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    ("pmx_population_destroy", None, [C.c_void_p]),
-    ("pmx_population_n_subjects", C.c_int64, [C.c_void_p]),
-    ("pmx_population_n_observations", C.c_int64, [C.c_void_p]),
-    ("pmx_population_n_events", C.c_int64, [C.c_void_p]),
-    ("pmx_population_device", C.c_int32, [C.c_void_p]),
-    ("pmx_population_observation_offsets", C.c_int32, [C.c_void_p, C.c_void_p]),
-    ("pmx_population_observation_info", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_model_create", C.c_int32, [_MD, C.POINTER(C.c_void_p)]),
-    ("pmx_model_create_custom", C.c_int32, [_MD, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
-    ("pmx_debug_jit_source", C.c_int32, [_MD, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
-    ("pmx_model_create_user", C.c_int32, [_MD, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
-    ("pmx_debug_jit_source_user", C.c_int32, [_MD, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
-    ("pmx_free_text", None, [C.c_void_p]),
-    ("pmx_jit_cache_stats", C.c_int32, [C.POINTER(_abi.pmx_jit_cache_counters)]),
-    ("pmx_jit_cache_clear", None, [C.c_int32]),
-    ("pmx_debug_jit_compile_big_lists", C.c_int32, [C.c_void_p]),
-    ("pmx_model_destroy", None, [C.c_void_p]),
-    ("pmx_predict", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    ("pmx_predict_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    ("pmx_prediction_buffer_create", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double)]),
-    ("pmx_prediction_buffer_create_pitched", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double)]),
-    ("pmx_prediction_buffer_destroy", None, [C.c_void_p]),
-    ("pmx_time_predict_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
-    ("pmx_predict_state_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    ("pmx_predict_batch", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_predict_batch_device", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_predict_stats_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_predict_batch_stats_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_loglik", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    ("pmx_loglik_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    ("pmx_loglik_batch", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_loglik_batch_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_mixture_loglik_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_dfunction_scratch_doubles", C.c_int64, [C.c_int64, C.c_int64]),
-    ("pmx_dfunction_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_mixture_loglik", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_dfunction", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_posterior_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    ("pmx_summarize_predictions_device", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-      C.c_void_p]),
-    ("pmx_summarize_predictions", C.c_int32,
-     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("pmx_recommended_ld", C.c_int64, [C.c_int64]),
-    ("pmx_measure_write_ceiling", C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
-    ("pmx_host_alloc", C.c_int32, [C.c_int64, C.POINTER(C.c_void_p)]),
-    ("pmx_host_free", None, [C.c_void_p]),
-    ("pmx_last_kernel_name", C.c_char_p, []),
-    ("pmx_last_error", C.c_char_p, []),
-    ("pmx_debug_compile", C.c_int32, [_PD, _MD, C.POINTER(_abi.pmx_op_stream_view)]),
-    ("pmx_debug_free", None, [C.POINTER(_abi.pmx_op_stream_view)]),
-    ("pmx_debug_class_plan", C.c_int32, [_PD, _MD, C.POINTER(C.c_int64)]),
-    ("pmx_debug_reload_env", None, []),
-]
+# every symbol include/pmx.h declares: (name, restype, argtypes), generated from the header (_pmx_h.py)
+SYMBOLS = _abi.FUNCTIONS
 
 
 def lib():
@@ -128,12 +42,24 @@ def lib():
             fn.argtypes = args
         if L.pmx_abi_version() != _abi.PMX_ABI_VERSION:
             raise ImportError("libpmx_hip.so ABI version mismatch")
-        if L.pmx_sizeof_model_desc() != C.sizeof(_abi.pmx_model_desc):
-            raise ImportError("pmx_model_desc layout drift between include/pmx.h and pharmsol_amd/_abi.py")
-        if L.pmx_sizeof_population_desc() != C.sizeof(_abi.pmx_population_desc):
-            raise ImportError("pmx_population_desc layout drift")
+        for st in _abi.STRUCTS:
+            if L.pmx_sizeof_struct(st.__name__.encode()) != C.sizeof(st):
+                raise ImportError(f"{st.__name__} layout drift between libpmx_hip.so and pharmsol_amd/_pmx_h.py")
         _lib = L
     return _lib
+
+
+class Owned:
+    """Base of the objects that own a library handle: ``handle`` goes back through the library function that ``_destroy``
+    names when the object is collected."""
+    _destroy = ""
+    handle = None
+
+    def __del__(self):
+        h = self.handle
+        if h and _lib is not None:  # (module globals vanish at interpreter exit)
+            getattr(_lib, self._destroy)(h)
+            self.handle = None
 
 
 def check(rc: int, allow_pair_failures: bool = False) -> int:

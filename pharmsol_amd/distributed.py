@@ -71,9 +71,10 @@ class ShardedPopulation:
         return runtime.DevicePopulation(self.flat, device, subjects=self.bounds[self.rank])
 
 
-class Communicator:
+class Communicator(_ffi.Owned):
     """``pmx_comm``: one RCCL rank per GPU.  The 128-byte id is made by rank 0 and shipped to the other ranks over the
     ``torch.distributed`` group the caller already has (any backend); a C / Rust caller uses its own transport."""
+    _destroy = "pmx_comm_destroy"
 
     def __init__(self, device: int, group=None):
         import torch
@@ -94,12 +95,6 @@ class Communicator:
         h = C.c_void_p()
         _ffi.check(L.pmx_comm_create(raw, self.world_size, self.rank, self.device, C.byref(h)))
         self.handle = h
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _ffi is not None and _ffi._lib is not None:
-            _ffi._lib.pmx_comm_destroy(h)
-            self.handle = None
 
 
 def full_prediction_tensor(sharded: ShardedPopulation, n_support: int, device=None, dtype=None):

@@ -20,10 +20,64 @@ def device_count() -> int:
     return int(_ffi.lib().pmx_device_count())
 
 
-class DeviceModel:
+def _desc(model) -> _abi.pmx_model_desc:
+    """The descriptor of a model, of a ``DeviceModel`` or a descriptor itself; makes no library call."""
+    dm = getattr(model, "_handle", None)  # (first: the case of every call after a model's first)
+    if dm is not None or isinstance(model, DeviceModel):
+        return (dm or model).desc
+    return model if isinstance(model, _abi.pmx_model_desc) else model.desc()
+
+
+def _theta(theta, nparams: int, dev):
+    """The theta front of every device entry point: numpy or torch in, a contiguous float64 CUDA matrix
+    ``[n_support, nparams]`` out.  Anything else is a ``ValueError``, raised before an upload or a library call."""
+    import torch
+
+    on_device = isinstance(theta, torch.Tensor) and theta.is_cuda
+    if not on_device:
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+    elif theta.dtype != torch.float64:
+        raise ValueError(f"theta is {theta.dtype}; the kernels read float64")
+    if theta.ndim != 2 or theta.shape[1] != nparams:
+        raise ValueError(f"theta has shape {tuple(theta.shape)}; the model takes [n_support, {nparams}]")
+    return theta.contiguous() if on_device else torch.as_tensor(theta, device=dev)
+
+
+def _host_theta(theta, nparams: int) -> np.ndarray:
+    """The same front for the host-pointer entry points: a contiguous float64 numpy matrix ``[n_support, nparams]``, a
+    1-D theta being one support point."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.ndim == 1:
+        theta = theta.reshape(1, -1)
+    if theta.ndim != 2 or theta.shape[1] != nparams:
+        raise ValueError(f"theta has shape {tuple(theta.shape)}; the model takes [n_support, {nparams}]")
+    return theta
+
+
+def _one_row_per_subject(theta, pop) -> None:
+    if theta.shape[0] != pop.n_subjects:
+        raise ValueError(f"batch form needs one theta row per subject: {theta.shape[0]} rows, {pop.n_subjects} subjects")
+
+
+def _ld(m, n_columns: int) -> int:
+    """Leading dimension of a matrix whose rows are contiguous: the row stride, or ``n_columns`` when there is one row
+    (a single row's stride says nothing)."""
+    return m.stride(0) if m.dim() == 2 and m.size(0) > 1 else n_columns
+
+
+def _stream(dev) -> int:
+    """torch's current stream on the population's device, as the ``hipStream_t`` the library takes."""
+    import torch
+
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class DeviceModel(_ffi.Owned):
+    _destroy = "pmx_model_destroy"
+
     def __init__(self, model):
         self.model = model
-        self.desc = model.desc() if not isinstance(model, _abi.pmx_model_desc) else model
+        self.desc = _desc(model)
         h = C.c_void_p()
         src = getattr(model, "source", None)
         if src is not None and getattr(model, "user_fns", 0):  # user closures of an analytical model (hiprtc)
@@ -35,14 +89,10 @@ class DeviceModel:
             _ffi.check(_ffi.lib().pmx_model_create(C.byref(self.desc), C.byref(h)))
         self.handle = h
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _ffi is not None and _ffi._lib is not None:  # (module globals vanish at interpreter exit)
-            _ffi._lib.pmx_model_destroy(h)
-            self.handle = None
 
+class DevicePopulation(_ffi.Owned):
+    _destroy = "pmx_population_destroy"
 
-class DevicePopulation:
     def __init__(self, flat: FlatPopulation, device: int = 0, subjects: Optional[Tuple[int, int]] = None):
         """``subjects=(s0, s1)``: only that subject range of ``flat`` (``pmx_population_create_shard``: one rank's shard
         of a population every rank holds on the host, no re-based copy)."""
@@ -72,12 +122,6 @@ class DevicePopulation:
         _ffi.check(_ffi.lib().pmx_population_observation_info(self.handle, t.ctypes.data, o.ctypes.data, s.ctypes.data))
         return t, o, s
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h and _ffi is not None and _ffi._lib is not None:
-            _ffi._lib.pmx_population_destroy(h)
-            self.handle = None
-
 
 def alloc_predictions(model, pop: DevicePopulation, theta, tries: int = 4, reps: int = 5, log=None):
     """A prediction matrix ``[n_observations, n_support]`` placed where the kernel writes fastest.
@@ -90,10 +134,9 @@ def alloc_predictions(model, pop: DevicePopulation, theta, tries: int = 4, reps:
     import torch
 
     dev = torch.device("cuda", pop.device)
-    if not (isinstance(theta, torch.Tensor) and theta.is_cuda):
-        theta = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float64), device=dev)
-    theta = theta.contiguous()
-    P = int(theta.shape[0])
+    theta = _theta(theta, _desc(model).nparams, dev)
+    P = theta.size(0)
+    dm, stream = _as_model(model), _stream(dev)
     best, best_ms, held = None, float("inf"), []
     for _ in range(max(1, tries)):
         try:
@@ -103,11 +146,10 @@ def alloc_predictions(model, pop: DevicePopulation, theta, tries: int = 4, reps:
         held.append(cand)
         ms_c = C.c_double()
         if len(held) == 1:  # bring the device clocks up first, or the first candidate is judged on a cold device
-            _ffi.check(_ffi.lib().pmx_time_predict_device(_as_model(model).handle, pop.handle, theta.data_ptr(), P,
-                                                          cand.data_ptr(), P, 40, torch.cuda.current_stream(dev).cuda_stream,
-                                                          C.byref(ms_c)))
-        _ffi.check(_ffi.lib().pmx_time_predict_device(_as_model(model).handle, pop.handle, theta.data_ptr(), P, cand.data_ptr(),
-                                                      P, reps, torch.cuda.current_stream(dev).cuda_stream, C.byref(ms_c)))
+            _ffi.check(_ffi.lib().pmx_time_predict_device(dm.handle, pop.handle, theta.data_ptr(), P, cand.data_ptr(), P, 40,
+                                                          stream, C.byref(ms_c)))
+        _ffi.check(_ffi.lib().pmx_time_predict_device(dm.handle, pop.handle, theta.data_ptr(), P, cand.data_ptr(), P, reps,
+                                                      stream, C.byref(ms_c)))
         ms = ms_c.value
         if log is not None:
             log.append((int(cand.data_ptr()), ms))
@@ -120,18 +162,14 @@ def alloc_predictions(model, pop: DevicePopulation, theta, tries: int = 4, reps:
     return best
 
 
-class _PlacedBuffer:
+class _PlacedBuffer(_ffi.Owned):
     """Device memory owned by ``pmx_prediction_buffer_create``, exposed to torch through ``__cuda_array_interface__``."""
+    _destroy = "pmx_prediction_buffer_destroy"
 
-    def __init__(self, ptr: int, shape, ms: float):
-        self.ptr, self.shape, self.ms_per_pass = int(ptr), tuple(int(x) for x in shape), float(ms)
-        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": "<f8", "data": (self.ptr, False), "version": 3,
+    def __init__(self, handle: C.c_void_p, shape, ms: float):
+        self.handle, self.shape, self.ms_per_pass = handle, tuple(int(x) for x in shape), float(ms)
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": "<f8", "data": (handle.value, False), "version": 3,
                                          "strides": None}
-
-    def __del__(self):
-        if getattr(self, "ptr", 0) and _ffi is not None and _ffi._lib is not None:
-            _ffi._lib.pmx_prediction_buffer_destroy(C.c_void_p(self.ptr))
-            self.ptr = 0
 
 
 def place_predictions(model, pop: DevicePopulation, theta, search_gib: float = 48.0, exhaustive: bool = False, ld: int = 0):
@@ -144,18 +182,15 @@ def place_predictions(model, pop: DevicePopulation, theta, search_gib: float = 4
     import torch
 
     dev = torch.device("cuda", pop.device)
-    if not (isinstance(theta, torch.Tensor) and theta.is_cuda):
-        theta = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float64), device=dev)
-    theta = theta.contiguous()
-    P = int(theta.shape[0])
+    theta = _theta(theta, _desc(model).nparams, dev)
+    P = theta.size(0)
     out, ms = C.c_void_p(), C.c_double()
     pitch = max(int(ld), P)
     with torch.cuda.device(dev):
         _ffi.check(_ffi.lib().pmx_prediction_buffer_create_pitched(_as_model(model).handle, pop.handle, theta.data_ptr(), P, pitch,
                                                                    int(search_gib * (1 << 30)) * (-1 if exhaustive else 1),
-                                                                   torch.cuda.current_stream(dev).cuda_stream, C.byref(out),
-                                                                   C.byref(ms)))
-    owner = _PlacedBuffer(out.value, (pop.n_observations, pitch), ms.value)
+                                                                   _stream(dev), C.byref(out), C.byref(ms)))
+    owner = _PlacedBuffer(out, (pop.n_observations, pitch), ms.value)
     base = torch.as_tensor(owner, device=dev)
     base._pmx_owner = owner
     if pitch == P:
@@ -176,16 +211,14 @@ def predict_states(model, pop: DevicePopulation, theta, states=None):
     per state on torch's current stream."""
     import torch
 
+    dev = torch.device("cuda", pop.device)
+    theta = _theta(theta, _desc(model).nparams, dev)
+    P = theta.size(0)
     L = _ffi.lib()
     dm = _as_model(model)
-    dev = torch.device("cuda", pop.device)
-    if not (isinstance(theta, torch.Tensor) and theta.is_cuda):
-        theta = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float64), device=dev)
-    theta = theta.contiguous()
-    P = int(theta.shape[0])
     states = list(range(dm.desc.nstates)) if states is None else [int(s) for s in states]
     out = torch.empty((len(states), pop.n_observations, P), dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _stream(dev)
     for k, st in enumerate(states):
         _ffi.check(L.pmx_predict_state_device(dm.handle, pop.handle, theta.data_ptr(), P, st, out[k].data_ptr(), P, None,
                                               stream))
@@ -195,7 +228,7 @@ def predict_states(model, pop: DevicePopulation, theta, states=None):
 def jit_translation_unit(model) -> str:
     """The source text the library hands to hiprtc for a custom ODE model (``pmx_debug_jit_source``)."""
     L = _ffi.lib()
-    d = model.desc()
+    d = _desc(model)
     out = C.c_void_p()
     if getattr(model, "user_fns", 0):
         _ffi.check(L.pmx_debug_jit_source_user(C.byref(d), model.source.encode(), int(model.user_fns), C.byref(out)))
@@ -245,17 +278,12 @@ def _check_host(rc: int, status: np.ndarray, dm, raise_on_pair_failure: bool) ->
 def predict_host(model, flat: FlatPopulation, theta: np.ndarray, device: int = 0, batch: bool = False,
                  raise_on_pair_failure: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """Host-pointer ABI form (``pmx_predict`` / ``pmx_predict_batch``): numpy in, numpy out."""
+    theta = _host_theta(theta, _desc(model).nparams)
     L = _ffi.lib()
     dm = _as_model(model)
     pop = DevicePopulation(flat, device)
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    if theta.ndim == 1:
-        theta = theta.reshape(1, -1)
-    if theta.shape[1] != dm.desc.nparams:
-        raise ValueError(f"theta has {theta.shape[1]} columns, model declares {dm.desc.nparams} parameters")
     if batch:
-        if theta.shape[0] != pop.n_subjects:
-            raise ValueError("batch form needs one theta row per subject")
+        _one_row_per_subject(theta, pop)
         pred = np.full((pop.n_observations,), np.nan)
         status = np.zeros((pop.n_subjects,), dtype=np.uint8)
         rc = L.pmx_predict_batch(dm.handle, pop.handle, theta.ctypes.data, pred.ctypes.data, status.ctypes.data)
@@ -276,67 +304,50 @@ def predict(model, pop: DevicePopulation, theta, pred=None, status=None, batch: 
     (batch: ``[n_subjects, 4]``) of accepted explicit steps, accepted implicit steps, rejected attempts and switches."""
     import torch
 
-    L = _ffi.lib()
-    dm = _as_model(model)
     dev = torch.device("cuda", pop.device)
-    if not (isinstance(theta, torch.Tensor) and theta.is_cuda):
-        theta = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float64), device=dev)
-    theta = theta.contiguous()
-    assert theta.dtype == torch.float64 and theta.dim() == 2 and theta.shape[1] == dm.desc.nparams
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    stats = None
-    if solver_stats:
-        if dm.desc.ode_solver != _abi.PMX_SOLVER_AUTO:
-            raise ValueError("solver_stats=True needs a model of with_solver('auto')")
-        n_pairs = (pop.n_subjects,) if batch else (pop.n_subjects, int(theta.shape[0]))
-        stats = torch.zeros(n_pairs + (4,), dtype=torch.int32, device=dev)
+    theta = _theta(theta, _desc(model).nparams, dev)
+    dm = _as_model(model)
+    if solver_stats and dm.desc.ode_solver != _abi.PMX_SOLVER_AUTO:
+        raise ValueError("solver_stats=True needs a model of with_solver('auto')")
     if batch:
-        assert theta.shape[0] == pop.n_subjects
-        if pred is None:
-            pred = torch.empty((pop.n_observations,), dtype=torch.float64, device=dev)
-        if status is None and want_status:
-            status = torch.zeros((pop.n_subjects,), dtype=torch.uint8, device=dev)
-        if solver_stats:
-            rc = L.pmx_predict_batch_stats_device(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(),
-                                                  status.data_ptr() if status is not None else None, stream, stats.data_ptr())
-        else:
-            rc = L.pmx_predict_batch_device(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(),
-                                            status.data_ptr() if status is not None else None, stream)
+        _one_row_per_subject(theta, pop)
+        shape = ()
     else:
-        P = int(theta.shape[0])
-        if pred is None:
-            pred = torch.empty((pop.n_observations, P), dtype=torch.float64, device=dev)
+        P = theta.size(0)
+        shape = (P,)
+    if pred is None:
+        pred = torch.empty((pop.n_observations,) + shape, dtype=torch.float64, device=dev)
+    if status is None and want_status:
+        status = torch.zeros((pop.n_subjects,) + shape, dtype=torch.uint8, device=dev)
+    stats = torch.zeros((pop.n_subjects,) + shape + (4,), dtype=torch.int32, device=dev) if solver_stats else None
+    # one entry point out of four: the batch forms take neither n_support nor ld_pred, the stats forms one pointer more
+    entry = getattr(_ffi.lib(), _PREDICT_ENTRY[batch, solver_stats])
+    d_status, tail = status.data_ptr() if status is not None else None, (stats.data_ptr(),) if solver_stats else ()
+    if batch:
+        rc = entry(dm.handle, pop.handle, theta.data_ptr(), pred.data_ptr(), d_status, _stream(dev), *tail)
+    else:
         assert pred.is_contiguous() or pred.stride(1) == 1
-        ld = int(pred.stride(0)) if pred.dim() == 2 and pred.shape[0] > 1 else P
-        if status is None and want_status:
-            status = torch.zeros((pop.n_subjects, P), dtype=torch.uint8, device=dev)
-        if solver_stats:
-            rc = L.pmx_predict_stats_device(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), ld,
-                                            status.data_ptr() if status is not None else None, stream, stats.data_ptr())
-        else:
-            rc = L.pmx_predict_device(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), ld,
-                                      status.data_ptr() if status is not None else None, stream)
+        rc = entry(dm.handle, pop.handle, theta.data_ptr(), P, pred.data_ptr(), _ld(pred, P), d_status, _stream(dev), *tail)
     _ffi.check(rc)
-    if solver_stats:
-        return pred, status, stats
-    return pred, status
+    return (pred, status, stats) if solver_stats else (pred, status)
+
+
+_PREDICT_ENTRY = {(False, False): "pmx_predict_device", (False, True): "pmx_predict_stats_device",
+                  (True, False): "pmx_predict_batch_device", (True, True): "pmx_predict_batch_stats_device"}
 
 
 def loglik_host(model, flat: FlatPopulation, error_models, theta: np.ndarray, device: int = 0,
                 raise_on_pair_failure: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """Host-pointer form of the fused log-likelihood (``pmx_loglik``): ``(ll[S, P], status[S, P])``."""
+    theta = _host_theta(theta, _desc(model).nparams)
     L = _ffi.lib()
     dm = _as_model(model)
     pop = DevicePopulation(flat, device)
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    if theta.ndim == 1:
-        theta = theta.reshape(1, -1)
     P = theta.shape[0]
     em = error_models.to_c(model)
     ll = np.full((pop.n_subjects, P), np.nan)
     status = np.zeros((pop.n_subjects, P), dtype=np.uint8)
-    rc = L.pmx_loglik(dm.handle, pop.handle, C.cast(em, C.c_void_p), theta.ctypes.data, P, ll.ctypes.data, P,
-                      status.ctypes.data)
+    rc = L.pmx_loglik(dm.handle, pop.handle, em, theta.ctypes.data, P, ll.ctypes.data, P, status.ctypes.data)
     _check_host(rc, status, dm, raise_on_pair_failure)
     return ll, status
 
@@ -345,16 +356,15 @@ def loglik_batch_host(model, flat: FlatPopulation, error_models, theta: np.ndarr
                       ) -> Tuple[np.ndarray, np.ndarray]:
     """Host-pointer batch form (``pmx_loglik_batch``): subject s under theta row s; ``(ll[S], status[S])``, failed
     subjects = -inf (likelihood/mod.rs:137-140)."""
+    theta = _host_theta(theta, _desc(model).nparams)
     L = _ffi.lib()
     dm = _as_model(model)
     pop = DevicePopulation(flat, device)
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    assert theta.shape == (pop.n_subjects, dm.desc.nparams)
+    _one_row_per_subject(theta, pop)
     em = error_models.to_c(model)
     ll = np.full((pop.n_subjects,), np.nan)
     status = np.zeros((pop.n_subjects,), dtype=np.uint8)
-    _ffi.check(L.pmx_loglik_batch(dm.handle, pop.handle, C.cast(em, C.c_void_p), theta.ctypes.data, ll.ctypes.data,
-                                  status.ctypes.data))
+    _ffi.check(L.pmx_loglik_batch(dm.handle, pop.handle, em, theta.ctypes.data, ll.ctypes.data, status.ctypes.data))
     return ll, status
 
 
@@ -379,23 +389,17 @@ def loglik(model, pop: DevicePopulation, error_models, theta, ll=None, status=No
     (likelihood/matrix.rs:52-106), support point fastest."""
     import torch
 
-    L = _ffi.lib()
-    dm = _as_model(model)
     dev = torch.device("cuda", pop.device)
-    if not (isinstance(theta, torch.Tensor) and theta.is_cuda):
-        theta = torch.as_tensor(np.ascontiguousarray(theta, dtype=np.float64), device=dev)
-    theta = theta.contiguous()
-    P = int(theta.shape[0])
+    theta = _theta(theta, _desc(model).nparams, dev)
+    P = theta.size(0)
+    dm = _as_model(model)
     if ll is None:
         ll = torch.empty((pop.n_subjects, P), dtype=torch.float64, device=dev)
     if status is None and want_status:
         status = torch.zeros((pop.n_subjects, P), dtype=torch.uint8, device=dev)
-    em = error_models if not hasattr(error_models, "to_c") else error_models.to_c(model)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = L.pmx_loglik_device(dm.handle, pop.handle, C.cast(em, C.c_void_p), theta.data_ptr(), P, ll.data_ptr(),
-                             int(ll.stride(0)) if ll.shape[0] > 1 else P,
-                             status.data_ptr() if status is not None else None, stream)
-    _ffi.check(rc)
+    em = error_models.to_c(model) if hasattr(error_models, "to_c") else error_models  # or a ready pmx_error_model array
+    _ffi.check(_ffi.lib().pmx_loglik_device(dm.handle, pop.handle, em, theta.data_ptr(), P, ll.data_ptr(), _ld(ll, P),
+                                            status.data_ptr() if status is not None else None, _stream(dev)))
     return ll, status
 
 
@@ -404,7 +408,7 @@ def _ll_matrix(pop: DevicePopulation, ll):
     assert ll.is_cuda and ll.dtype.is_floating_point and ll.element_size() == 8 and ll.dim() == 2
     assert ll.shape[0] == pop.n_subjects and ll.stride(1) == 1
     P = int(ll.shape[1])
-    return P, (int(ll.stride(0)) if ll.shape[0] > 1 else P)
+    return P, _ld(ll, P)
 
 
 def _device_vector(x, n: int, dev):
@@ -429,7 +433,7 @@ def mixture_loglik(pop: DevicePopulation, ll, w, out=None):
         out = torch.empty((pop.n_subjects,), dtype=torch.float64, device=dev)
     assert out.dtype == torch.float64 and out.shape == (pop.n_subjects,) and out.stride(0) == 1
     _ffi.check(_ffi.lib().pmx_mixture_loglik_device(pop.handle, ll.data_ptr(), P, ld, w.data_ptr(), out.data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream))
+                                                    _stream(dev)))
     return out
 
 
@@ -448,7 +452,7 @@ def d_function(pop: DevicePopulation, ll, log_pyl, out=None):
     L = _ffi.lib()
     scratch = torch.empty((max(int(L.pmx_dfunction_scratch_doubles(pop.n_subjects, P)), 1),), dtype=torch.float64, device=dev)
     _ffi.check(L.pmx_dfunction_device(pop.handle, ll.data_ptr(), P, ld, log_pyl.data_ptr(), scratch.data_ptr(), out.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream))
+                                      _stream(dev)))
     return out
 
 
@@ -468,7 +472,7 @@ def posterior(pop: DevicePopulation, ll, w, log_pyl, out=None):
     assert out.shape == (pop.n_subjects, P)
     _, ld_out = _ll_matrix(pop, out)
     _ffi.check(_ffi.lib().pmx_posterior_device(pop.handle, ll.data_ptr(), P, ld, w.data_ptr(), log_pyl.data_ptr(),
-                                               out.data_ptr(), ld_out, torch.cuda.current_stream(dev).cuda_stream))
+                                               out.data_ptr(), ld_out, _stream(dev)))
     return out
 
 
@@ -484,7 +488,7 @@ def summarize_predictions(pop: DevicePopulation, pred, w, ll=None, log_pyl=None,
     assert pred.is_cuda and pred.dtype == torch.float64 and pred.dim() == 2 and pred.stride(1) == 1
     assert pred.shape[0] == pop.n_observations
     P = int(pred.shape[1])
-    ld_pred = int(pred.stride(0)) if pred.shape[0] > 1 else P
+    ld_pred = _ld(pred, P)
     w = _device_vector(w, P, dev)
     if (ll is None) != (log_pyl is None):
         raise ValueError("ll and log_pyl go together: both (posterior) or neither (population)")
@@ -500,7 +504,7 @@ def summarize_predictions(pop: DevicePopulation, pred, w, ll=None, log_pyl=None,
     _ffi.check(_ffi.lib().pmx_summarize_predictions_device(
         pop.handle, pred.data_ptr(), P, ld_pred, w.data_ptr(), ll.data_ptr() if ll is not None else None, ld_ll,
         log_pyl.data_ptr() if ll is not None else None, out_mean.data_ptr() if mean else None,
-        out_median.data_ptr() if median else None, torch.cuda.current_stream(dev).cuda_stream))
+        out_median.data_ptr() if median else None, _stream(dev)))
     return out_mean, out_median
 
 
@@ -511,7 +515,7 @@ def last_kernel_name() -> str:
 def class_plan(model, flat: FlatPopulation) -> dict:
     """Host-side introspection (``pmx_debug_class_plan``): how the analytical GRID kernels would batch this
     population.  Needs no GPU."""
-    md = model.desc() if not isinstance(model, _abi.pmx_model_desc) else model
+    md = _desc(model)
     pd = flat.desc()
     counts = (C.c_int64 * 5)()
     _ffi.check(_ffi.lib().pmx_debug_class_plan(C.byref(pd), C.byref(md), counts))
@@ -523,7 +527,7 @@ def compile_ops(model, flat: FlatPopulation) -> dict:
     """Host-side introspection (``pmx_debug_compile``): the op stream the device would walk, as numpy
     arrays.  Needs no GPU."""
     L = _ffi.lib()
-    md = model.desc() if not isinstance(model, _abi.pmx_model_desc) else model
+    md = _desc(model)
     pd = flat.desc()
     v = _abi.pmx_op_stream_view()
     _ffi.check(L.pmx_debug_compile(C.byref(pd), C.byref(md), C.byref(v)))

@@ -1,5 +1,6 @@
 """bindings/rust/pmx_sys.rs (the `extern "C"` block a pharmsol maintainer links against) is generated
-from include/pmx.h by tools/gen_rust_binding.py.  Rust cannot be compiled in this image, so the file is checked instead:
+from include/pmx.h by tools/gen_rust_binding.py (the header's parser, tools/pmx_header.py, is shared with the Python
+binding's generator: tests/test_python_binding.py).  Rust cannot be compiled in this image, so the file is checked instead:
 it is in sync with the header, every `#[repr(C)]` struct has the C layout (field order, offsets and sizeof computed
 with the repr(C) rules and compared with ctypes' view of the same header and with the library's own
 pmx_sizeof_struct()), and every function the header declares is bound and exported."""
