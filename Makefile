@@ -8,7 +8,7 @@ LIB := pharmsol_amd/lib/libpmx_hip.so
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 DEVFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-parameter -Iinclude
 # the kernel units: one translation unit per kernel family (pmx_lanes.hpp lists them)
-KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util pmx_mixture pmx_posterior
+KUNITS := pmx_grid pmx_dyn3 pmx_steps pmx_pair pmx_classed pmx_classed_ll pmx_ode_builtin pmx_util pmx_mixture pmx_posterior pmx_exposure
 OBJ := $(CSRC)/build/pmx_compile.o $(CSRC)/build/pmx_plan.o $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_model.o $(CSRC)/build/pmx_host.o $(CSRC)/build/pmx_stream.o $(CSRC)/build/pmx_launch.o $(KUNITS:%=$(CSRC)/build/%.o) $(CSRC)/build/pmx_jit.o $(CSRC)/build/pmx_jit_source.o $(CSRC)/build/pmx_jit_cache.o $(CSRC)/build/pmx_alloc.o $(CSRC)/build/pmx_shard.o
 DEVHDR := $(CSRC)/pmx_devtypes.hpp $(CSRC)/pmx_device.hpp $(CSRC)/pmx_ode.hpp $(CSRC)/pmx_structures.hpp $(CSRC)/pmx_userlag.hpp $(CSRC)/pmx_analytical.hpp $(CSRC)/pmx_ode_user.hpp include/pmx.h
 
@@ -27,7 +27,7 @@ $(CSRC)/build/pmx_api.o $(CSRC)/build/pmx_model.o $(CSRC)/build/pmx_host.o $(CSR
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -ffp-contract=off -x hip -c $< -o $@
 
-KHDR := $(CSRC)/pmx_lanes.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_solvers.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
+KHDR := $(CSRC)/pmx_lanes.hpp $(CSRC)/pmx_kernels.hpp $(CSRC)/pmx_weights.hpp $(CSRC)/pmx_solvers.hpp $(CSRC)/pmx_compile.hpp $(DEVHDR)
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(KHDR)
 	@mkdir -p $(CSRC)/build
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@
@@ -105,3 +105,8 @@ tests/cpp/jit_source_fingerprint_san: tests/cpp/jit_source_fingerprint.cpp $(JIT
 tests/cpp/facade_test: tests/cpp/facade_test.cpp include/pharmsol_hip.hpp include/pmx.h $(LIB) oracle
 	g++ -O1 -std=c++17 -Wall -Wextra -o $@ tests/cpp/facade_test.cpp -Lpharmsol_amd/lib -lpmx_hip -Loracle/_build -lpmx_oracle \
 	    -Wl,-rpath,'$$ORIGIN/../../pharmsol_amd/lib' -Wl,-rpath,'$$ORIGIN/../../oracle/_build' -Wl,-rpath,/opt/rocm/lib
+
+# the façade's exposure / attainment call (tests/test_cpp_exposure.py compares its output with the Python path)
+tests/cpp/exposure_facade_test: tests/cpp/exposure_facade_test.cpp include/pharmsol_hip.hpp include/pmx.h $(LIB)
+	g++ -O1 -std=c++17 -Wall -Wextra -o $@ tests/cpp/exposure_facade_test.cpp -Lpharmsol_amd/lib -lpmx_hip \
+	    -Wl,-rpath,'$$ORIGIN/../../pharmsol_amd/lib' -Wl,-rpath,/opt/rocm/lib

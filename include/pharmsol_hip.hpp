@@ -450,6 +450,19 @@ class Equation {
                                double* mean, double* median, uint8_t* status, bool throw_on_pair_failure = false) {
       check(pmx_summarize_predictions(eq_.handle(), pop_, error_models.data(), theta, n_support, w, mean, median, status), !throw_on_pair_failure);
     }
+    /// profiles: the prediction rows of one (subject, occasion, output equation); what exposure_attainment's outputs are indexed by
+    int64_t n_profiles() const { return pmx_population_n_profiles(pop_); }
+    /// per profile the probability of target attainment (metric >= target[profile]) and the weighted mean of ONE exposure
+    /// metric (a PMX_EXPO_* bit) over the support points, weighted by w (error_models null) or by the posterior of the
+    /// profile's subject; target and pta go together, either output may be null
+    void exposure_attainment(const double* theta, int64_t n_support, const double* w, const std::vector<pmx_error_model>* error_models,
+                             int32_t method, double t_start, double t_end, double threshold, uint32_t metric, const double* target,
+                             double* pta, double* mean, uint8_t* status, bool throw_on_pair_failure = false) {
+      const double window[3] = {t_start, t_end, threshold};
+      check(pmx_exposure_attainment(eq_.handle(), pop_, error_models ? error_models->data() : nullptr, theta, n_support, w, method,
+                                    window, metric, target, pta, mean, status),
+            !throw_on_pair_failure);
+    }
     const pmx_population* handle() const { return pop_; }
 
    private:

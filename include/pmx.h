@@ -334,6 +334,13 @@ int32_t pmx_population_observation_offsets(const pmx_population* pop, int64_t* o
 /* Per prediction row: time / outeq / subject of the observation, in prediction
  * order (what Observation::to_prediction re-attaches, event.rs:698-711). Any pointer may be NULL. */
 int32_t pmx_population_observation_info(const pmx_population* pop, double* time, int32_t* outeq, int64_t* subject);
+/* Profiles: the prediction rows of one (subject, occasion, output equation), in prediction order - what the exposure
+ * metrics below are taken of.  Ordered by subject, then occasion position within the subject, then outeq ascending; only
+ * combinations with at least one row exist.  The table is built at the first call that needs it.  -1: NULL. */
+int64_t pmx_population_n_profiles(const pmx_population* pop);
+/* per profile, any pointer may be NULL: subject, occasion (position within the subject), outeq, number of rows */
+int32_t pmx_population_profile_info(const pmx_population* pop, int64_t* subject, int64_t* occasion, int32_t* outeq,
+                                    int64_t* n_rows);
 
 /* Replaces Analytical::new(...).with_nstates()... / ODE::new(...) (analytical/mod.rs:102-152, ode/mod.rs:115-166). */
 int32_t pmx_model_create(const pmx_model_desc* desc, pmx_model** out);
@@ -659,6 +666,66 @@ int32_t pmx_summarize_predictions_device(const pmx_population* pop, const double
 int32_t pmx_summarize_predictions(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em /*or NULL*/,
                                   const double* theta, int64_t n_support, const double* w, double* mean /*or NULL*/,
                                   double* median /*or NULL*/, uint8_t* status /*[n_subjects x n_support] or NULL*/);
+
+/* What a simulation takes of the matrix pmx_predict writes: per profile (pmx_population_profile_info) and support point
+ * the exposure metrics of the predicted curve, and over the support points the probability of target attainment.
+ *
+ * A profile's points are (t_i, c_i), i = 0..n-1: the observation times, non-decreasing, and the predictions.  The window
+ * [t_start, t_end] = [a, b], a < b; a = -inf and b = +inf mean the whole profile; a >= b or a NaN bound is an invalid
+ * argument.  The clipped profile K holds the points with a <= t_i <= b, with (a, lerp(a)) in front when a lies strictly
+ * inside a segment, t_{i-1} < a < t_i, and (b, lerp(b)) behind when b does; lerp(x) = v1 + (v2 - v1) * (x - t1) / (t2 - t1)
+ * in that form, v1 where |t2 - t1| < 1e-10 (data/auc.rs:357-361).  Every metric is the reference's whole-profile array
+ * function applied to K:
+ *   AUC         the sum over consecutive pairs of K of auc_segment_with_tmax (data/auc.rs:96-126): linear trapezoids,
+ *               (c1 - c2) dt / ln(c1 / c2) where the method and use_log_linear (auc.rs:28-30, its 1e-10 test included)
+ *               say so; for PMX_AUC_LIN_LOG tmax is the time of the first-occurrence maximum of the UNCLIPPED profile,
+ *               as auc_interval takes it (auc.rs:250)
+ *   AUMC        the same with aumc_segment_with_tmax (auc.rs:130-160)
+ *   TIME_ABOVE  nca/calc.rs:719-737 on K: the >= rule, both crossing forms
+ *   CMAX, TMAX  the first-occurrence maximum of K (a `c > max` fold) and its time; CMIN the first-occurrence minimum
+ * AUC over K is auc_interval(times, values, a, b) bit for bit when no two times coincide.  One difference: at a duplicate
+ * time exactly at the window start the reference skips that zero-length segment and K keeps it (AUC and AUMC are NaN).
+ * Edges, per (profile, support point).  A NaN prediction anywhere in the profile, inside the window or not, makes every
+ * requested metric NaN (failed pairs write NaN rows).  A zero-length pair in K: AUC and AUMC are NaN (the reference's
+ * InvalidTimeSequence), the others are unaffected.  Fewer than two points in K: AUC, AUMC and TIME_ABOVE are NaN
+ * (InsufficientData); exactly one: CMAX = CMIN = its value, TMAX = its time; none: everything NaN.  Nothing is truncated
+ * at the last positive value (no AllBelowLOQ): a profile of zeros has AUC 0.  +-inf predictions follow IEEE through the
+ * formulas as written.
+ *
+ * d_out: one plane per set bit of `metrics`, in bit order; plane k is [n_profiles] rows ld_out >= n_support doubles apart,
+ * planes n_profiles*ld_out apart; columns [n_support, ld_out) are never written.  The three scalars of type double
+ * travel by address (every by-value parameter of this ABI is an integer): `window` is three doubles in HOST memory,
+ * {t_start, t_end, threshold}, read before the call returns; NULL means the whole profile and no threshold.  The
+ * threshold is read only with PMX_EXPO_TIME_ABOVE (NaN or no window there: invalid argument).  Stream-ordered, not
+ * synchronised; 8-byte alignment is all any device pointer needs; bit-identical from run to run, for any alignment and
+ * any ld. */
+enum { PMX_AUC_LINEAR = 0, PMX_AUC_LIN_UP_LOG_DOWN = 1, PMX_AUC_LIN_LOG = 2 }; /* AUCMethod's order (data/event.rs) */
+enum { PMX_EXPO_AUC = 1, PMX_EXPO_AUMC = 2, PMX_EXPO_CMAX = 4, PMX_EXPO_TMAX = 8, PMX_EXPO_CMIN = 16,
+       PMX_EXPO_TIME_ABOVE = 32, PMX_EXPO_ALL = 63 };
+int32_t pmx_exposure_device(const pmx_population* pop, const double* d_pred, int64_t n_support, int64_t ld_pred,
+                            int32_t method, const double* window /*host: t_start, t_end, threshold; or NULL*/,
+                            uint32_t metrics, double* d_out, int64_t ld_out, void* stream);
+/* pta[k]  = sum_{p: q > 0, m[k][p] >= target[k]} q / sum_{p: q > 0} q
+ * mean[k] = sum_{p: q > 0} q m[k][p] / sum_{p: q > 0} q
+ * over one metric plane m [n_profiles] rows ld_metric doubles apart; q as in pmx_summarize_predictions_device: w itself
+ * (d_ll == NULL, then d_lpyl NULL too) or the posterior of the profile's subject.  At least one of d_pta (then d_target is
+ * required) and d_mean; each [n_profiles].  A target is "at least" only: the caller of an upper limit takes the complement.
+ * Edges as for the summaries: a column with w == 0 is skipped whatever it holds; a negative or NaN weight gives NaN
+ * everywhere; a NaN q - a failed pair under weight - gives NaN for every profile of that subject and for no other
+ * subject's; a NaN metric under q > 0 gives NaN for that profile only; a profile whose q are all 0 gives NaN.  Summed in
+ * a fixed order: bit-identical from run to run, for any alignment and any ld. */
+int32_t pmx_attainment_device(const pmx_population* pop, const double* d_metric, int64_t n_support, int64_t ld_metric,
+                              const double* d_target, const double* d_w, const double* d_ll, int64_t ld_ll,
+                              const double* d_lpyl, double* d_pta, double* d_mean, void* stream);
+/* Host form: theta in, n_profiles doubles out per output; neither the matrix nor a metric plane crosses the link.  Runs
+ * predict, then - em given - loglik and the mixture rows, then the exposure of the one metric, then the attainment.
+ * Errors and status as for pmx_summarize_predictions: w is checked before any work, and with failed pairs the call returns
+ * PMX_ERR_PAIR_FAILED, the status array (if given) is filled and the outputs are still copied out. */
+int32_t pmx_exposure_attainment(const pmx_model* model, const pmx_population* pop, const pmx_error_model* em /*or NULL*/,
+                                const double* theta, int64_t n_support, const double* w, int32_t method,
+                                const double* window /*t_start, t_end, threshold; or NULL*/, uint32_t metric /*exactly one bit*/,
+                                const double* target /*[n_profiles], NULL iff pta is*/, double* pta /*or NULL*/,
+                                double* mean /*or NULL*/, uint8_t* status /*or NULL*/);
 
 /* Row pitch (ld_pred, in doubles) at which the prediction kernels write fastest: n_support rounded up to a multiple of 16,
  * so every row starts on a 128-byte boundary.  Measured on C3 (profiles/r03/ld_by_allocation.txt): 1000 -> 1008 doubles

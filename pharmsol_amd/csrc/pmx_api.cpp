@@ -139,6 +139,26 @@ int32_t pmx_population_observation_info(const pmx_population* pop, double* time,
   return PMX_OK;
 }
 
+int64_t pmx_population_n_profiles(const pmx_population* pop) {
+  if (!pop) return -1;
+  host_profiles(const_cast<pmx_population*>(pop));
+  return pop->profiles.n();
+}
+
+int32_t pmx_population_profile_info(const pmx_population* pop, int64_t* subject, int64_t* occasion, int32_t* outeq,
+                                    int64_t* n_rows) {
+  if (!pop) return fail(PMX_ERR_INVALID_ARGUMENT, "null population");
+  host_profiles(const_cast<pmx_population*>(pop));
+  const auto& pr = pop->profiles;
+  const size_t n = static_cast<size_t>(pr.n());
+  if (subject) std::memcpy(subject, pr.subject.data(), sizeof(int64_t) * n);
+  if (occasion) std::memcpy(occasion, pr.occasion.data(), sizeof(int64_t) * n);
+  if (outeq) std::memcpy(outeq, pr.outeq.data(), sizeof(int32_t) * n);
+  if (n_rows)
+    for (size_t k = 0; k < n; ++k) n_rows[k] = pr.off[k + 1] - pr.off[k];
+  return PMX_OK;
+}
+
 }  // extern "C"
 
 // ---- device-pointer forms -------------------------------------------------------------------------------------------
@@ -164,6 +184,12 @@ struct DeviceCall {
   }
 };
 bool matrix_ok(int64_t n_support, int64_t ld) { return n_support > 0 && ld >= n_support; }
+
+// method, window, threshold and metric bits of an exposure call (exposure_refusal, pmx_internal.hpp)
+Arg exposure_request(int32_t method, const double* window, uint32_t metrics) {
+  const char* why = exposure_refusal(method, window, metrics);
+  return {why == nullptr, why};
+}
 
 // the model of a *_stats_device call integrates with PMX_SOLVER_AUTO (checked before any other pointer, and before any device is touched)
 Arg stats_model(const pmx_model* model) {
@@ -310,6 +336,43 @@ int32_t pmx_summarize_predictions_device(const pmx_population* cpop, const doubl
   const pmx::SummaryArgs a{d_pred, c.pop->hp.n_obs, n_support, ld_pred, d_w, d_ll, ld_ll, d_lpyl, c.pop->d_subj_obs_off,
                            c.pop->hp.n_subjects, c.pop->max_subject_rows, d_mean, d_median};
   PMX_HIP(pmx::launch_summary_rows(a, stream));
+  return PMX_OK;
+}
+
+// the exposure metrics of a matrix pmx_predict_device wrote, and their attainment (pmx_exposure.hip)
+int32_t pmx_exposure_device(const pmx_population* cpop, const double* d_pred, int64_t n_support, int64_t ld_pred,
+                            int32_t method, const double* window, uint32_t metrics, double* d_out, int64_t ld_out,
+                            void* stream) {
+  DeviceCall c;
+  int32_t rc = c.begin(cpop, {{cpop && d_pred && d_out, kNull},
+                              {matrix_ok(n_support, ld_pred), "n_support must be > 0 and ld_pred >= n_support"},
+                              {ld_out >= n_support, "ld_out must be >= n_support"},
+                              exposure_request(method, window, metrics)});
+  if (rc != PMX_OK) return rc;
+  if ((rc = resident_profiles(c.pop)) != PMX_OK) return rc;
+  const auto& pr = c.pop->profiles;
+  const ExposureWindow win(window);
+  const pmx::ExposureArgs a{d_pred, n_support, ld_pred, pr.d_off, pr.d_row, pr.d_time, pr.n(), method,
+                            win.a, win.b, win.threshold, metrics, d_out, ld_out};
+  PMX_HIP(pmx::launch_exposure(a, stream));
+  return PMX_OK;
+}
+
+int32_t pmx_attainment_device(const pmx_population* cpop, const double* d_metric, int64_t n_support, int64_t ld_metric,
+                              const double* d_target, const double* d_w, const double* d_ll, int64_t ld_ll,
+                              const double* d_lpyl, double* d_pta, double* d_mean, void* stream) {
+  DeviceCall c;
+  int32_t rc = c.begin(cpop, {{cpop && d_metric && d_w, kNull},
+                              {d_pta || d_mean, "d_pta and d_mean are both null: nothing to compute"},
+                              {!d_pta || d_target, "d_pta needs d_target"},
+                              {(d_ll == nullptr) == (d_lpyl == nullptr), "d_ll and d_lpyl go together: both (posterior) or neither (population)"},
+                              {matrix_ok(n_support, ld_metric), "n_support must be > 0 and ld_metric >= n_support"},
+                              {!d_ll || ld_ll >= n_support, "ld_ll must be >= n_support"}});
+  if (rc != PMX_OK) return rc;
+  if ((rc = resident_profiles(c.pop)) != PMX_OK) return rc;
+  const auto& pr = c.pop->profiles;
+  const pmx::AttainArgs a{d_metric, pr.n(), n_support, ld_metric, d_target, d_w, d_ll, ld_ll, d_lpyl, pr.d_subject, d_pta, d_mean};
+  PMX_HIP(pmx::launch_attainment(a, stream));
   return PMX_OK;
 }
 

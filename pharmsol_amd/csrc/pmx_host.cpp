@@ -1,5 +1,5 @@
 // pmx_host.cpp — the HOST-pointer entry points of include/pmx.h: pmx_predict, pmx_predict_batch, pmx_loglik,
-// pmx_loglik_batch, pmx_mixture_loglik, pmx_dfunction, pmx_summarize_predictions.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
+// pmx_loglik_batch, pmx_mixture_loglik, pmx_dfunction, pmx_summarize_predictions, pmx_exposure_attainment.  Each uploads theta, runs the same enqueue as its *_device twin on a private stream and copies the
 // result out.
 #include <cstring>
 #include <limits>
@@ -407,6 +407,61 @@ int32_t pmx_summarize_predictions(const pmx_model* model, const pmx_population* 
   const size_t out_bytes = static_cast<size_t>(n_obs) * sizeof(double);
   if (mean && (rc = ws_copy_out(ws, mean, out_bytes, d_mean, out_bytes, 1)) != PMX_OK) return rc;
   if (median && (rc = ws_copy_out(ws, median, out_bytes, d_median, out_bytes, 1)) != PMX_OK) return rc;
+  return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
+}
+
+// predict, then - posterior mode - loglik and the mixture rows, then the one exposure metric and its attainment
+// (pmx_exposure.hip), all on the private stream: pred stays in the workspace's output matrix, the metric plane and the
+// small vectors in its reduction buffer [w | lpyl | target | pta | mean | plane | ll], and n_profiles doubles come back
+// per requested output.
+int32_t pmx_exposure_attainment(const pmx_model* model, const pmx_population* cpop, const pmx_error_model* em,
+                                const double* theta, int64_t n_support, const double* w, int32_t method,
+                                const double* window, uint32_t metric, const double* target, double* pta, double* mean,
+                                uint8_t* status) {
+  pmx::clear_error();
+  if (!model || !cpop || !theta || !w) return fail(PMX_ERR_INVALID_ARGUMENT, "null argument");
+  if (!pta && !mean) return fail(PMX_ERR_INVALID_ARGUMENT, "pta and mean are both null: nothing to compute");
+  if ((pta == nullptr) != (target == nullptr)) return fail(PMX_ERR_INVALID_ARGUMENT, "pta and target go together");
+  if (n_support <= 0) return fail(PMX_ERR_INVALID_ARGUMENT, "n_support must be > 0");
+  if (const char* why = exposure_refusal(method, window, metric)) return fail(PMX_ERR_INVALID_ARGUMENT, why);
+  if ((metric & (metric - 1)) != 0) return fail(PMX_ERR_INVALID_ARGUMENT, "metric must be exactly one PMX_EXPO_* bit");
+  int32_t rc = check_weights(w, n_support);
+  if (rc != PMX_OK) return rc;
+  pmx_population* pop = const_cast<pmx_population*>(cpop);
+  const int64_t S = pop->hp.n_subjects, n_obs = pop->hp.n_obs, P = n_support;
+  HostCall call;
+  if ((rc = call.begin(model, pop, theta, P, 0, n_obs)) != PMX_OK) return rc;
+  if ((rc = call.run(model, pop, P, 0)) != PMX_OK) return rc;
+  if ((rc = resident_profiles(pop)) != PMX_OK) return rc;
+  const auto& pr = pop->profiles;
+  const int64_t n = pr.n();
+  HostWorkspace* ws = call.ws;
+  const size_t n_red = static_cast<size_t>(P + S + 3 * n + n * P + (em ? S * P : 0));
+  if ((rc = ws_reserve(&ws->d_red, &ws->red_cap, n_red * sizeof(double))) != PMX_OK) return rc;
+  double* d_w = static_cast<double*>(ws->d_red);
+  double* d_lpyl = d_w + P;
+  double* d_target = d_lpyl + S;
+  double* d_pta = d_target + n;
+  double* d_mean = d_pta + n;
+  double* d_plane = d_mean + n;
+  double* d_ll = d_plane + n * P;
+  const size_t out_bytes = static_cast<size_t>(n) * sizeof(double);
+  PMX_HIP(hipMemcpyAsync(d_w, w, static_cast<size_t>(P) * sizeof(double), hipMemcpyHostToDevice, ws->compute));
+  if (target && n > 0) PMX_HIP(hipMemcpyAsync(d_target, target, out_bytes, hipMemcpyHostToDevice, ws->compute));
+  if (em) {
+    if ((rc = loglik_into(call, model, pop, em, P, 0, d_ll)) != PMX_OK) return rc;
+    PMX_HIP(pmx::launch_mixture_rows(d_ll, S, P, P, d_w, d_lpyl, ws->compute));
+  }
+  const ExposureWindow win(window);
+  const pmx::ExposureArgs ea{call.d_out(), P, P, pr.d_off, pr.d_row, pr.d_time, n, method, win.a, win.b, win.threshold, metric, d_plane, P};
+  PMX_HIP(pmx::launch_exposure(ea, ws->compute));
+  const pmx::AttainArgs aa{d_plane, n, P, P, pta ? d_target : nullptr, d_w, em ? d_ll : nullptr, P, em ? d_lpyl : nullptr,
+                           pr.d_subject, pta ? d_pta : nullptr, mean ? d_mean : nullptr};
+  PMX_HIP(pmx::launch_attainment(aa, ws->compute));
+  bool any_failed = false;
+  if ((rc = ws_finish_status(ws, status, call.n_status, &any_failed)) != PMX_OK) return rc;
+  if (pta && (rc = ws_copy_out(ws, pta, out_bytes, d_pta, out_bytes, 1)) != PMX_OK) return rc;
+  if (mean && (rc = ws_copy_out(ws, mean, out_bytes, d_mean, out_bytes, 1)) != PMX_OK) return rc;
   return any_failed ? fail(PMX_ERR_PAIR_FAILED, kPairFailed) : PMX_OK;
 }
 

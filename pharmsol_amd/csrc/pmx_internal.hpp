@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <deque>
 #include <map>
 #include <memory>
@@ -161,6 +162,23 @@ struct pmx_population {
   // call (resident_obs_off), freed with ll_allocs
   const int64_t* d_subj_obs_off = nullptr;
   int64_t max_subject_rows = 0;
+  // the profile table, for the exposure metrics (pmx_exposure.hip): the prediction rows of every (subject, occasion,
+  // outeq) that has one, ordered by subject, occasion position, outeq.  Built on the host at the first call that asks
+  // for it (host_profiles), uploaded at the first device call (resident_profiles), freed with ll_allocs.
+  struct Profiles {
+    bool built = false;
+    std::vector<int64_t> off;       // [n + 1] into row / time
+    std::vector<int64_t> row;       // [n_obs] prediction rows in profile order
+    std::vector<double> time;       // [n_obs] their times
+    std::vector<int64_t> subject, occasion;  // [n]
+    std::vector<int32_t> outeq;     // [n]
+    const int64_t* d_off = nullptr;
+    const int64_t* d_row = nullptr;
+    const double* d_time = nullptr;
+    const int64_t* d_subject = nullptr;
+    bool resident = false;
+    int64_t n() const { return static_cast<int64_t>(subject.size()); }
+  } profiles;
   std::vector<std::unique_ptr<DeviceStream>> streams;  // one per model flavour, built lazily
   pmx_population();
   ~pmx_population();  // (pmx_host.cpp, where HostWorkspace is complete; pmx_population_destroy too)
@@ -201,6 +219,25 @@ int32_t acquire_ll_slot(const pmx_model* model, pmx_population* pop, DeviceStrea
 void release_ll_slot(pmx_population* pop, DeviceStream::LLCache* slot, void* stream);
 // pop->d_subj_obs_off / max_subject_rows, uploaded once per population (the population's device is current)
 int32_t resident_obs_off(pmx_population* pop);
+// pop->profiles: the host table (pure host work, once per population) / the host table and its device copy (the
+// population's device is current)
+void host_profiles(pmx_population* pop);
+int32_t resident_profiles(pmx_population* pop);
+// nullptr, or why the scalars of an exposure call are refused: method, window, threshold, metric bits (both forms)
+// (window: {t_start, t_end, threshold} on the host, or null for the whole profile and no threshold)
+inline const char* exposure_refusal(int32_t method, const double* window, uint32_t metrics) {
+  if (method < PMX_AUC_LINEAR || method > PMX_AUC_LIN_LOG) return "method must be one of PMX_AUC_*";
+  if (metrics == 0 || (metrics & ~static_cast<uint32_t>(PMX_EXPO_ALL)) != 0) return "metrics must be a non-empty set of PMX_EXPO_* bits";
+  if (window && !(window[0] < window[1])) return "the window needs t_start < t_end (neither NaN)";
+  if ((metrics & PMX_EXPO_TIME_ABOVE) && (!window || window[2] != window[2]))
+    return "threshold is NaN or not given and PMX_EXPO_TIME_ABOVE is requested";
+  return nullptr;
+}
+struct ExposureWindow {
+  double a, b, threshold;
+  explicit ExposureWindow(const double* w)
+      : a(w ? w[0] : -HUGE_VAL), b(w ? w[1] : HUGE_VAL), threshold(w ? w[2] : 0.0) {}
+};
 
 // ---- pmx_launch.cpp
 // What the model contributes to the op stream, under this snapshot of the switches, on a population with / without

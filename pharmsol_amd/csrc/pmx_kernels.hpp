@@ -193,6 +193,42 @@ struct SummaryArgs {
 };
 hipError_t launch_summary_rows(const SummaryArgs& a, void* stream);
 
+// The exposure metrics of every (profile, support point) of a prediction matrix, and their attainment over the support
+// points (pmx_exposure.hip; the arithmetic: include/pmx.h).  The profile table lives on the device: the rows of profile k
+// are prof_row[prof_off[k] .. prof_off[k + 1]) with times prof_time[...], in prediction order.
+//   A wave owns 64 consecutive columns of one profile, a lane one column; a block is four such waves, consecutive items
+//   of the list (profile, column tile) with the column tile fastest.  One plane of `out` per set bit of `metrics`.
+struct ExposureArgs {
+  const double* pred;
+  int64_t P, ld_pred;
+  const int64_t* prof_off;  // [n_profiles + 1]
+  const int64_t* prof_row;  // [n_obs]
+  const double* prof_time;  // [n_obs]
+  int64_t n_profiles;
+  int32_t method;       // PMX_AUC_*
+  double a, b, threshold;
+  uint32_t metrics;     // PMX_EXPO_* bits
+  double* out;
+  int64_t ld_out;
+};
+hipError_t launch_exposure(const ExposureArgs& a, void* stream);
+//   pta[k] and mean[k] of the metric row of profile k under q = w (ll, lpyl null) or the posterior of prof_subject[k]:
+//   a wave owns a row up to kAttainWaveMax columns, a block of four beyond
+constexpr int64_t kAttainWaveMax = 1024;
+struct AttainArgs {
+  const double* metric;
+  int64_t n_profiles, P, ld_metric;
+  const double* target;  // [n_profiles], with pta
+  const double* w;
+  const double* ll;      // null: population mode
+  int64_t ld_ll;
+  const double* lpyl;
+  const int64_t* prof_subject;  // [n_profiles], on the device (posterior mode)
+  double* pta;           // [n_profiles] or null
+  double* mean;          // [n_profiles] or null
+};
+hipError_t launch_attainment(const AttainArgs& a, void* stream);
+
 // One entry per kernel family, at the end of the family's translation unit (pmx_grid.hip, pmx_classed.hip, ...): it
 // switches on the model's kernel id and the route's variant flags and enqueues that instantiation.  Policy-free: which
 // family, which variant and which geometry is the route's (pmx_launch.cpp plan_routes).

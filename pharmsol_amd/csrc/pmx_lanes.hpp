@@ -8,6 +8,7 @@
 //   pmx_util.hip                                                 log-likelihood tables, status scan, streaming fill
 //   pmx_mixture.hip                                              reductions of the log-likelihood matrix: mixture rows, D-function
 //   pmx_posterior.hip                                            posterior rows; weighted mean and median of the prediction rows
+//   pmx_exposure.hip                                             exposure metrics per (profile, support point); target attainment
 //
 // One wavefront lane per (subject, support point) pair, two lane mappings:
 //

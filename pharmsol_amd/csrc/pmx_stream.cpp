@@ -1,7 +1,9 @@
 // pmx_stream.cpp — the device side of a (population, model flavour) pair: plan on the host (pmx_compile.cpp
 // plan_stream), upload, and the log-likelihood's sigma-table slots.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
 
 #include "pmx_internal.hpp"
 
@@ -229,6 +231,62 @@ int32_t resident_obs_off(pmx_population* pop) {
   const int32_t rc = upload(off, &pop->d_subj_obs_off, &pop->ll_allocs);
   if (rc == PMX_OK) pop->max_subject_rows = most;
   return rc;
+}
+
+namespace {
+
+// under pop->mu.  Prediction rows are the observations in event order, so a walk over a subject's occasions counts them;
+// within an occasion a stable sort by outeq keeps each profile's rows in prediction order.
+void build_profiles(pmx_population* pop) {
+  auto& pr = pop->profiles;
+  if (pr.built) return;
+  const auto& hp = pop->hp;
+  pr.off.assign(1, 0);
+  pr.row.reserve(static_cast<size_t>(hp.n_obs));
+  pr.time.reserve(static_cast<size_t>(hp.n_obs));
+  std::vector<std::pair<int32_t, int64_t>> obs;  // (outeq, row) of one occasion
+  for (int64_t s = 0; s < hp.n_subjects; ++s) {
+    int64_t r = hp.subj_obs_off[static_cast<size_t>(s)];
+    for (int64_t o = hp.subj_occ_off[static_cast<size_t>(s)]; o < hp.subj_occ_off[static_cast<size_t>(s) + 1]; ++o) {
+      obs.clear();
+      for (int64_t e = hp.occ_ev_off[static_cast<size_t>(o)]; e < hp.occ_ev_off[static_cast<size_t>(o) + 1]; ++e)
+        if (hp.ev_kind[static_cast<size_t>(e)] == PMX_EV_OBSERVATION) obs.emplace_back(hp.ev_io[static_cast<size_t>(e)], r++);
+      std::stable_sort(obs.begin(), obs.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+      for (size_t k = 0; k < obs.size(); ++k) {
+        if (k == 0 || obs[k].first != obs[k - 1].first) {
+          if (k > 0) pr.off.push_back(static_cast<int64_t>(pr.row.size()));
+          pr.subject.push_back(s);
+          pr.occasion.push_back(o - hp.subj_occ_off[static_cast<size_t>(s)]);
+          pr.outeq.push_back(obs[k].first);
+        }
+        pr.row.push_back(obs[k].second);
+        pr.time.push_back(hp.obs_time[static_cast<size_t>(obs[k].second)]);
+      }
+      if (!obs.empty()) pr.off.push_back(static_cast<int64_t>(pr.row.size()));
+    }
+  }
+  pr.built = true;
+}
+
+}  // namespace
+
+void host_profiles(pmx_population* pop) {
+  std::lock_guard<std::mutex> lock(pop->mu);
+  build_profiles(pop);
+}
+
+int32_t resident_profiles(pmx_population* pop) {
+  std::lock_guard<std::mutex> lock(pop->mu);
+  build_profiles(pop);
+  auto& pr = pop->profiles;
+  if (pr.resident) return PMX_OK;
+  Uploader up{&pop->ll_allocs};
+  up(pr.off, &pr.d_off);
+  up(pr.row, &pr.d_row);
+  up(pr.time, &pr.d_time);
+  up(pr.subject, &pr.d_subject);
+  if (up.rc == PMX_OK) pr.resident = true;
+  return up.rc;
 }
 
 void release_ll_slot(pmx_population* pop, DeviceStream::LLCache* slot, void* stream) {

@@ -122,6 +122,20 @@ class DevicePopulation(_ffi.Owned):
         _ffi.check(_ffi.lib().pmx_population_observation_info(self.handle, t.ctypes.data, o.ctypes.data, s.ctypes.data))
         return t, o, s
 
+    @property
+    def n_profiles(self) -> int:
+        return int(_ffi.lib().pmx_population_n_profiles(self.handle))
+
+    def profiles(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``(subject, occasion, outeq, n_rows)`` of every profile - the prediction rows of one (subject, occasion,
+        output equation) - in the order the exposure metrics come in (``pmx_population_profile_info``)."""
+        n = self.n_profiles
+        s, o, n_rows = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        q = np.zeros(n, dtype=np.int32)
+        _ffi.check(_ffi.lib().pmx_population_profile_info(self.handle, s.ctypes.data, o.ctypes.data, q.ctypes.data,
+                                                          n_rows.ctypes.data))
+        return s, o, q, n_rows
+
 
 def alloc_predictions(model, pop: DevicePopulation, theta, tries: int = 4, reps: int = 5, log=None):
     """A prediction matrix ``[n_observations, n_support]`` placed where the kernel writes fastest.
@@ -506,6 +520,89 @@ def summarize_predictions(pop: DevicePopulation, pred, w, ll=None, log_pyl=None,
         log_pyl.data_ptr() if ll is not None else None, out_mean.data_ptr() if mean else None,
         out_median.data_ptr() if median else None, _stream(dev)))
     return out_mean, out_median
+
+
+EXPOSURE_METRICS = {"auc": _abi.PMX_EXPO_AUC, "aumc": _abi.PMX_EXPO_AUMC, "cmax": _abi.PMX_EXPO_CMAX, "tmax": _abi.PMX_EXPO_TMAX,
+                    "cmin": _abi.PMX_EXPO_CMIN, "time_above": _abi.PMX_EXPO_TIME_ABOVE}  # in plane (bit) order
+AUC_METHODS = {"linear": _abi.PMX_AUC_LINEAR, "lin_up_log_down": _abi.PMX_AUC_LIN_UP_LOG_DOWN, "lin_log": _abi.PMX_AUC_LIN_LOG}
+
+
+def _prediction_matrix(pop: DevicePopulation, pred):
+    """``(n_columns, ld)`` of a prediction matrix ``[n_observations, n_columns]`` whose rows are contiguous."""
+    import torch
+
+    assert pred.is_cuda and pred.dtype == torch.float64 and pred.dim() == 2 and pred.stride(1) == 1
+    assert pred.shape[0] == pop.n_observations
+    P = int(pred.shape[1])
+    return P, _ld(pred, P)
+
+
+def exposure(pop: DevicePopulation, pred, metrics=("auc", "aumc", "cmax", "tmax", "cmin"), method: str = "linear", window=None,
+             threshold=None, out=None) -> dict:
+    """The exposure metrics of every (profile, support point) of ``pred[n_observations, P]`` (``pmx_exposure_device``):
+    a dict of name -> tensor ``[n_profiles, P]``, views of one planes buffer (``out``, or a new one, ``[n_metrics,
+    n_profiles, P]``).  ``metrics``: names of ``EXPOSURE_METRICS``; ``method``: a name of ``AUC_METHODS``; ``window``:
+    ``(t_start, t_end)``, ``None`` for the whole profile; ``threshold``: the concentration of ``"time_above"``.  The
+    profiles are ``pop.profiles()``.  CUDA tensors on torch's current stream, not synchronised."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    P, ld_pred = _prediction_matrix(pop, pred)
+    names = [m for m in EXPOSURE_METRICS if m in set(metrics)]
+    if len(names) != len(set(metrics)) or not names:
+        raise ValueError(f"metrics must be a non-empty subset of {tuple(EXPOSURE_METRICS)}")
+    if method not in AUC_METHODS:
+        raise ValueError(f"method must be one of {tuple(AUC_METHODS)}")
+    if "time_above" in names and threshold is None:
+        raise ValueError("'time_above' needs a threshold")
+    a, b = (-np.inf, np.inf) if window is None else (float(window[0]), float(window[1]))
+    bits = 0
+    for m in names:
+        bits |= EXPOSURE_METRICS[m]
+    n = pop.n_profiles
+    if out is None:
+        out = torch.empty((len(names), n, P), dtype=torch.float64, device=dev)
+    assert out.is_cuda and out.dtype == torch.float64 and out.shape == (len(names), n, P) and out.stride(2) == 1
+    ld_out = out.stride(1) if n > 1 else P
+    assert len(names) == 1 or out.stride(0) == n * ld_out
+    scalars = (C.c_double * 3)(a, b, float("nan") if threshold is None else float(threshold))  # (read before the call returns)
+    _ffi.check(_ffi.lib().pmx_exposure_device(pop.handle, pred.data_ptr(), P, ld_pred, AUC_METHODS[method], C.addressof(scalars),
+                                              bits, out.data_ptr(), ld_out, _stream(dev)))
+    return {m: out[k] for k, m in enumerate(names)}
+
+
+def target_attainment(pop: DevicePopulation, metric, w, target=None, ll=None, log_pyl=None, mean: bool = False):
+    """``(pta, mean)`` per profile of one metric plane ``metric[n_profiles, P]`` over the support points
+    (``pmx_attainment_device``): the share of the weight whose metric is at least ``target[n_profiles]`` and the
+    weighted mean, weighted by ``w`` or - ``ll`` and ``log_pyl`` given - by the posterior of the profile's subject.
+    ``None`` for an output that was not requested (``pta`` when there is no ``target``).  CUDA tensors of length
+    ``n_profiles`` on torch's current stream, not synchronised."""
+    import torch
+
+    dev = torch.device("cuda", pop.device)
+    n = pop.n_profiles
+    assert metric.is_cuda and metric.dtype == torch.float64 and metric.dim() == 2 and metric.stride(1) == 1
+    assert metric.shape[0] == n
+    P = int(metric.shape[1])
+    w = _device_vector(w, P, dev)
+    if (ll is None) != (log_pyl is None):
+        raise ValueError("ll and log_pyl go together: both (posterior) or neither (population)")
+    if target is None and not mean:
+        raise ValueError("neither a target nor the mean requested")
+    ld_ll = 0
+    if ll is not None:
+        P_ll, ld_ll = _ll_matrix(pop, ll)
+        assert P_ll == P
+        log_pyl = _device_vector(log_pyl, pop.n_subjects, dev)
+    if target is not None:
+        target = _device_vector(target, n, dev)
+    out_pta = torch.empty((n,), dtype=torch.float64, device=dev) if target is not None else None
+    out_mean = torch.empty((n,), dtype=torch.float64, device=dev) if mean else None
+    _ffi.check(_ffi.lib().pmx_attainment_device(
+        pop.handle, metric.data_ptr(), P, _ld(metric, P), target.data_ptr() if target is not None else None, w.data_ptr(),
+        ll.data_ptr() if ll is not None else None, ld_ll, log_pyl.data_ptr() if ll is not None else None,
+        out_pta.data_ptr() if target is not None else None, out_mean.data_ptr() if mean else None, _stream(dev)))
+    return out_pta, out_mean
 
 
 def last_kernel_name() -> str:
